@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mpixels/s decoded on 4K 4:2:2 restart-interval JPEGs (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the line.  --full adds everything else the
+benchmark measures or checks: the oracle comparison, single-frame latency, the host-fed pipeline
+(`end_to_end`, `host_feed_scaling`), the CPU baselines and the other BASELINE configurations.
+--dump-outputs DIR writes a fixed sample of what the last timed step computed as float32 .npy files.
 
 One process per GPU.  For N > 1 the driver launches this file through
 torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment);
@@ -59,6 +64,12 @@ def parse_args():
     p.add_argument("--preprocess", choices=["host", "device", "device-per-step"], default="host",
                    help="where scans are preprocessed: host at upload (the reference's data flow, default), "
                         "scan kernels once at upload, or scan kernels inside every timed step")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline figure, run every other record (oracle comparison, single_frame, end_to_end, "
+                        "host_feed_scaling, cpu_baseline, other_configs); --cpu-seconds, --no-verify, --no-sweep, --e2e-reps, "
+                        "--no-extra-configs and --host-feed-ranks shape those records and act only with it")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write a fixed, seeded sample of the last step's RGBA output to DIR/*.npy")
     p.add_argument("--cpu-seconds", type=float, default=12.0,
                    help="budget for the CPU-oracle baseline sample (0 disables it)")
     p.add_argument("--no-verify", action="store_true")
@@ -98,6 +109,40 @@ def make_inputs(args, rank, world, threads):
     with ThreadPoolExecutor(threads) as ex:
         jpegs = list(ex.map(one, range(distinct)))
     return [jpegs[i % distinct] for i in range(args.batch)], distinct
+
+
+DUMP_SEED = 0x5EED
+DUMP_SLOTS = 16
+DUMP_BYTES = 48 << 20   # everything dump_outputs writes: the RGBA sample and both index arrays (64 MB is the limit)
+
+
+def dump_outputs(batch, n_images, out_dir):
+    """--dump-outputs: what the timed path left in HBM after its last step, as a caller reads it back (Batch.read_output:
+    one RGBA8 image per slot), written as float32.  A step's output is 8.5 GB at the default size, so this is a fixed,
+    seeded sample within DUMP_BYTES: up to DUMP_SLOTS slots (the first, the last and a draw between) and in each the same
+    draw of pixels (every pixel where the frames are small enough).  Writes rgba_sample.npy (slots x pixels x 4, values 0..255) and the
+    slot and pixel indices it was drawn at (float64, row-major pixel index)."""
+    import numpy as np
+
+    rng = np.random.default_rng(DUMP_SEED)
+    if n_images <= DUMP_SLOTS:
+        slots = np.arange(n_images)
+    else:
+        between = rng.choice(np.arange(1, n_images - 1), DUMP_SLOTS - 2, replace=False)
+        slots = np.unique(np.concatenate([[0, n_images - 1], between]))
+    first = batch.read_output(int(slots[0]))
+    npix = first.shape[0] * first.shape[1]
+    # a drawn pixel costs 4 float32 in every slot and one float64 index; the slot indices are float64 too
+    per_slot = max(1, (DUMP_BYTES - 8 * len(slots)) // (len(slots) * 4 * 4 + 8))
+    pix = np.arange(npix) if per_slot >= npix else np.sort(rng.choice(npix, per_slot, replace=False))
+    rgba = np.empty((len(slots), len(pix), 4), np.float32)
+    for k, s in enumerate(slots):
+        img = first if k == 0 else batch.read_output(int(s))
+        rgba[k] = img.reshape(-1, 4)[pix]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rgba_sample.npy"), rgba)
+    np.save(os.path.join(out_dir, "rgba_sample_slots.npy"), slots.astype(np.float64))
+    np.save(os.path.join(out_dir, "rgba_sample_pixels.npy"), pix.astype(np.float64))
 
 
 def cpu_baseline(jpegs, budget_s, pixels_per_image):
@@ -615,6 +660,8 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     if args.gpus > 1 and world == 1:
         raise SystemExit("for --gpus N > 1 launch through torch.distributed.run (one rank per GPU)")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -705,8 +752,12 @@ def main():
     elapsed = max_over_ranks(elapsed, device="cpu" if args.rehearse_on_one_gpu else "cuda")
 
     # ---- everything below is outside the timed region -----------------------------------
+    if args.dump_outputs and rank == 0:
+        dump_outputs(batch, args.batch, args.dump_outputs)
+
+    # ---- and everything below, but the line itself, runs with --full only ----------------
     verified = None
-    if not args.no_verify and rank == 0:
+    if args.full and not args.no_verify and rank == 0:
         import numpy as np
         from oracle import oracle as orc
         # a spread of output slots (first, last, middle ones) against the oracle output of each slot's source;
@@ -726,7 +777,7 @@ def main():
     # the host-fed path (JPEG bytes in host memory -> RGBA in HBM) as a two-deep pipeline, every rank its own --
     # reported beside `value`, never as it
     end_to_end = None
-    if args.e2e_reps > 0:
+    if args.full and args.e2e_reps > 0:
         barrier()
         e2e = bench_end_to_end(compeg_amd, local_rank, jpegs, images, threads, args.e2e_reps, ext)
         barrier()
@@ -742,7 +793,7 @@ def main():
 
     # single-frame latency (BASELINE config 2: one 4K frame), device-only and end-to-end
     single = None
-    if rank == 0:
+    if args.full and rank == 0:
         one = compeg_amd.Batch(gpu)
         one.upload(images[:1], host_threads=1)
         for _ in range(5):
@@ -808,13 +859,13 @@ def main():
                                      "device_scan": {k: round(v, 1) for k, v in stages_dev.items()}}}
 
     base = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         base = cpu_baseline(jpegs, args.cpu_seconds, args.width * args.height)
         base["host_nproc"] = os.cpu_count()
         base["all_cores"] = cpu_baseline_all_cores(jpegs, min(8.0, args.cpu_seconds), args.width * args.height)
 
     extra = None
-    if rank == 0 and world == 1 and not args.no_extra_configs and not ext:
+    if args.full and rank == 0 and world == 1 and not args.no_extra_configs and not ext:
         extra = {"configs[0] scan.dat": bench_scan_dat(compeg_amd, gpu, jpegs[0], args.width * args.height)}
         if base is not None:
             base["a1_scan_preprocess_only"] = extra["configs[0] scan.dat"]["a1_on_one_benchmark_frame"]
@@ -839,7 +890,7 @@ def main():
             "64 x 3840x2160 YUV 4:4:4 baseline JPEG, DRI=3, 16 distinct frames (extension layout, MCUs in pairs, an interval's last one alone)", sampling=(1, 1))
 
     feed_scaling = None
-    if rank == 0 and world == 1 and args.host_feed_ranks and end_to_end is not None and not ext:
+    if args.full and rank == 0 and world == 1 and args.host_feed_ranks and end_to_end is not None and not ext:
         best = max(v.get("jpeg_gbs_consumed", v.get("pcie_gbs", 0.0)) for v in end_to_end.values() if isinstance(v, dict))
         feed_scaling = bench_host_feed_scaling(args, [int(v) for v in args.host_feed_ranks.split(",") if v], best)
         end_to_end["host_feed_scaling"] = feed_scaling
@@ -884,6 +935,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "clock_prime": {"seconds": args.prime_seconds, "decodes": prime_decodes,
                             "what": "untimed decodes in front of the warmup steps: the card's launches get shorter for 30-40 ms after idle"},
             "ms_per_step": round(ms_per_step, 4),

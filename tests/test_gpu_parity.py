@@ -1216,7 +1216,7 @@ def test_bench_multi_rank_path_rehearsed_on_one_gpu(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--rehearse-on-one-gpu", "--batch", "6", "--width", "640", "--height", "360", "--cpu-seconds", "0",
-           "--no-extra-configs", "--e2e-reps", "1"]
+           "--no-extra-configs", "--e2e-reps", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1227,6 +1227,36 @@ def test_bench_multi_rank_path_rehearsed_on_one_gpu(tmp_path):
     e2e = j["end_to_end"]
     assert e2e["verified_bit_exact_vs_oracle"] is True and e2e["from_jpeg_bytes_parse_included"]["whole_job_mpix_s"] > 0
     assert j["config"]["images_per_gpu"] == 6
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """bench.py without --full: the headline figure alone (no record that --full adds), the steps it was asked for, and
+    --dump-outputs writing what the last timed step decoded -- every pixel of every slot of this small batch, equal to
+    the oracle's decode of the slot's synthetic frame."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "6",
+           "--width", "640", "--height", "360", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["full"] is False
+    assert j["value"] > 0 and j["ms_per_step"] > 0 and j["unit"] == "Mpixels/s" and j["higher_is_better"] is True
+    for key in ("cpu_baseline", "other_configs", "single_frame", "end_to_end", "verified_bit_exact_vs_oracle"):
+        assert j[key] is None, key
+    rgba = np.load(out / "rgba_sample.npy")
+    slots = np.load(out / "rgba_sample_slots.npy")
+    pix = np.load(out / "rgba_sample_pixels.npy")
+    assert np.array_equal(slots, np.arange(6)) and np.array_equal(pix, np.arange(640 * 360))
+    for s in range(6):
+        jpeg = synth.make_jpeg(640, 360, seed=0xC0FFEE + s, kind=0, quality=85, ri=4, sampling=(2, 1))
+        want = orc.ImageData(jpeg).decode().reshape(-1, 4).astype(np.float32)
+        assert np.array_equal(rgba[s], want), s
 
 
 def test_c_consumer_decodes_on_the_gpu(ca, gpu, tmp_path):

@@ -6,7 +6,7 @@
 ARGS="$1"; shift
 for round in 1 2 3; do
   for lib in "$@"; do
-    COMPEG_LIB="$PWD/$lib" python bench.py $ARGS --cpu-seconds 0 --no-verify 2>/dev/null | python -c "
+    COMPEG_LIB="$PWD/$lib" python bench.py $ARGS --full --cpu-seconds 0 --no-verify 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 print('%-28s us/frame %.3f  kernel_ms %.4f  single %.1f us' % ('$lib', d['ms_per_frame']*1e3, d['roofline']['kernel_ms'], d['single_frame']['kernel_ms']*1e3))"
