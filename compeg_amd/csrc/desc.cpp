@@ -15,6 +15,7 @@ namespace compeg {
 void fill_desc(const ImageData &img, ImageDesc &d);
 void fill_coop(const ImageData &img, ImageDesc &d);
 uint32_t max_wave_span(const uint32_t *starts, size_t nstarts, size_t nwords, uint32_t intervals, uint32_t group);
+bool walk_state_shared(const ImageDesc &a, const ImageDesc &b);
 
 void fill_desc(const ImageData &img, ImageDesc &d)
 {
@@ -146,6 +147,20 @@ void fill_coop(const ImageData &img, ImageDesc &d)
     d.coop_ok = md.restart_interval <= kCoopMaxRestart ? 1u : 0u;
 }
 
+// May two images of a batch whose LUT bytes are the same (compeg_batch::note_batch_properties: `uniform`) share one
+// set of walk tables and one flat walk grid?  A wave of walk_mcus_422_kernel's flat grid computes its WalkTabs once,
+// from the first image it walks, and its workgroup stages that image's walk tables (coop_body.h: coop_tables, walk_body.h:
+// walk_tabs) -- so everything those read from the descriptor, beside the LUT bytes, has to be the same: which tables
+// each component's codes come from (the selectors), where the direct tables lie, the entropy mode and the zero-stream
+// data units (quirk Q1).
+bool walk_state_shared(const ImageDesc &a, const ImageDesc &b)
+{
+    return memcmp(a.fast_table, b.fast_table, sizeof a.fast_table) == 0 &&
+           memcmp(a.dc_fast_table, b.dc_fast_table, sizeof a.dc_fast_table) == 0 &&
+           memcmp(a.dc_table, b.dc_table, sizeof a.dc_table) == 0 && memcmp(a.ac_table, b.ac_table, sizeof a.ac_table) == 0 &&
+           a.fast_off == b.fast_off && a.standard_entropy == b.standard_entropy && a.zero_du_ok == b.zero_du_ok &&
+           memcmp(a.zero_du, b.zero_du, sizeof a.zero_du) == 0;
+}
 
 uint32_t max_wave_span(const uint32_t *starts, size_t nstarts, size_t nwords, uint32_t intervals, uint32_t group)
 {

@@ -1153,6 +1153,17 @@ void compeg_batch::note_batch_properties(const ImageData *const *images, size_t 
     max_out_w = max_out_h = 0;
     // frames of one stream: the same number of restart intervals and byte-identical LUTs in every image
     // (the fused kernel's workgroups may then span image boundaries)
+    //
+    // What `uniform` promises is exactly that, and nothing about selectors, quantisers, geometry or the entropy mode.
+    // Which flat grid relies on what (waves_per_image != 0: a wave or workgroup walks units of several images):
+    // - fused_kernel_body (decode_fused_422_kernel; decode_fused_422_mcu_rec_kernel with mcu_uniform, whose records are
+    //   made per image) and fused_stream_kernel_body (the 4:2:2 and the layouts' streamed kernels): the workgroup stages
+    //   L1, L2 and the direct tables once, from one image -- the same bytes under `uniform` -- and s.l2_staged comes from
+    //   d.fast_off, which the L2 size decides: equal too.  Everything else (tables per component, quantisers, geometry,
+    //   entropy mode, windows, output) is read from the unit's own descriptor, unit by unit.
+    // - walk_mcus_422_kernel: a wave's WalkTabs and the workgroup's walk tables in LDS come from the first image it
+    //   walks -- they depend on the selectors, the entropy mode and the zero-stream data units as well.  Its flat grid
+    //   needs walk_shared (walk_state_shared, desc.cpp) on top of `uniform`.
     uniform = n > 0;
     for (size_t i = 0; i < n; i++) {
         const ImageData &img = *images[i], &first = *images[0];
@@ -2041,12 +2052,11 @@ Status compeg_batch::make_walk_tables(hipStream_t stream, size_t n)
     // (the walk goes through the walk tables too)
     const bool want = n > 0 && !generic_layout && use_fused_pipeline() &&
                       (mcu_route || (coop_r != 0 && use_coop_kernel(max_intervals, uint32_t(smallest), coop_r))) && !lab_env("COMPEG_NO_WALK_TABLES");
-    // one set for all: the same tables (uniform) used by the same components
+    // one set for all: the same tables (uniform) used by the same components -- the condition of the walk's flat grid too
     bool shared = uniform;
     for (size_t i = 1; i < n && shared; i++)
-        shared = memcmp(descs[i].fast_table, descs[0].fast_table, sizeof descs[0].fast_table) == 0 &&
-                 memcmp(descs[i].dc_fast_table, descs[0].dc_fast_table, sizeof descs[0].dc_fast_table) == 0 &&
-                 descs[i].fast_off == descs[0].fast_off;
+        shared = walk_state_shared(descs[i], descs[0]);
+    walk_shared = shared;
     if (want)
         CG_TRY(walk_tables.reserve(kWalkTableBytes * (shared ? 1 : n)));
     for (size_t i = 0; i < n; i++)
@@ -2175,7 +2185,7 @@ Status compeg_batch::decode(hipStream_t stream)
         if (fused && mcu_route) {
             // the walk, a lane per restart interval (streamed windows: any interval length), then a lane per MCU
             const ImageDesc *md = static_cast<const ImageDesc *>(mcu_descs.ptr);
-            CG_HIP(launch_walk_mcus(dd + at, m, max_intervals, plan_walk(max_intervals, m, max_l2, stream_mcu_words, min_restart_interval, uniform, descs[0].walk != nullptr),
+            CG_HIP(launch_walk_mcus(dd + at, m, max_intervals, plan_walk(max_intervals, m, max_l2, stream_mcu_words, min_restart_interval, uniform && walk_shared, descs[0].walk != nullptr),
                                     stream, static_cast<uint32_t *>(unit_queue.ptr)));
             if (timing && at == 0) {
                 CG_HIP(hipEventRecord(ev[1], stream));

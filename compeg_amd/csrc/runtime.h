@@ -53,6 +53,8 @@ struct PinnedBuffer {
 // Fills the kernel-facing descriptor from the reference-format metadata.
 // Pointers are left for the caller to set.
 void fill_desc(const ImageData &img, ImageDesc &d);
+// Whether two images may share one set of walk tables and one flat walk grid (desc.cpp).
+bool walk_state_shared(const ImageDesc &a, const ImageDesc &b);
 
 } // namespace compeg
 
@@ -152,6 +154,7 @@ struct compeg_batch {
     uint32_t max_restart_interval = 0;   // ... and the largest
     uint64_t total_waves = 0;            // units of 64 intervals over all images
     bool uniform = false; // same interval count and LUT bytes in every image (set by upload)
+    bool walk_shared = false; // uniform, and every image walk_state_shared with the first (set by make_walk_tables)
     // cooperative kernel: the restart interval all images share if every one of them qualifies (else 0), and the
     // largest word span of a wave's group of intervals
     uint32_t coop_r = 0;

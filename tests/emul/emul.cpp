@@ -22,6 +22,7 @@
 
 namespace compeg {
 void fill_desc(const ImageData &img, ImageDesc &d);
+bool walk_state_shared(const ImageDesc &a, const ImageDesc &b);
 uint32_t max_wave_span(const uint32_t *starts, size_t nstarts, size_t nwords, uint32_t intervals, uint32_t group);
 }
 using namespace compeg;
@@ -650,8 +651,39 @@ int emul_decode(const uint8_t *jpeg, size_t len, uint8_t *rgba, uint32_t tex_w, 
 }
 
 // emul_runner in.jpg out.rgba out.ac out.dc waves_per_block window_words l2_in_lds [tex_w tex_h]
+// `--walk-shared a.jpg std_a b.jpg std_b`: parses two JPEGs (std: 1 = COMPEG_PARSE_STANDARD_ENTROPY) and prints
+// "shared 0|1" -- walk_state_shared of their descriptors (desc.cpp), the condition of the walk route's flat grid.
+static int walk_shared_mode(char **argv)
+{
+    ImageDesc d[2];
+    for (int i = 0; i < 2; i++) {
+        FILE *f = fopen(argv[2 + 2 * i], "rb");
+        if (!f)
+            return 2;
+        std::vector<uint8_t> jpeg;
+        uint8_t buf[65536];
+        size_t n;
+        while ((n = fread(buf, 1, sizeof buf, f)) > 0)
+            jpeg.insert(jpeg.end(), buf, buf + n);
+        fclose(f);
+        ImageData *img = nullptr;
+        const unsigned flags = atoi(argv[3 + 2 * i]) ? COMPEG_PARSE_STANDARD_ENTROPY : 0u;
+        Status s = ImageData::parse(jpeg.data(), jpeg.size(), true, &img, flags);
+        if (!s.ok()) {
+            printf("error: %s\n", s.message.c_str());
+            return 1;
+        }
+        fill_desc(*img, d[i]);
+        delete img;
+    }
+    printf("shared %d\n", walk_state_shared(d[0], d[1]) ? 1 : 0);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 6 && strcmp(argv[1], "--walk-shared") == 0)
+        return walk_shared_mode(argv);
     if (argc < 8) {
         fprintf(stderr, "usage: %s in.jpg out.rgba out.ac out.dc waves window_words l2_in_lds [tex_w tex_h]\n", argv[0]);
         return 2;

@@ -423,6 +423,76 @@ def test_emulated_standard_entropy_extension(runner, tmp_path):
             assert np.array_equal(got, want), f"fused={fused} {w}x{h}: {(got != want).any(axis=2).sum()} pixels differ"
 
 
+def _flipped(jpeg, rng, flips):
+    j = bytearray(jpeg)
+    scan_at = jpeg.find(b"\xff\xda") + 14
+    for _ in range(flips):
+        pos = int(rng.integers(scan_at, len(j) - 2))
+        if j[pos] != 0xFF and j[pos - 1] != 0xFF:
+            j[pos] ^= 1 << int(rng.integers(0, 8))
+            if j[pos] == 0xFF:
+                j[pos] = 0xFE
+    return bytes(j)
+
+
+@pytest.mark.parametrize("name", sorted(synth.SELECTOR_SETS))
+def test_emulated_kernels_any_table_selectors(runner, tmp_path, name):
+    """Every emulated kernel with the components on other Huffman tables than the encoder's usual ones
+    (tools/synth.py: SELECTOR_SETS): the per-component tables of the descriptor, the walk tables' pairs and their L1
+    tables (coop_tables, walk_tabs), the zero-stream data units (quirk Q1) -- on valid and bit-flipped scans."""
+    tables = synth.SELECTOR_SETS[name]
+    rng = np.random.default_rng(sum(map(ord, name)))
+    frames = [synth.make_jpeg(160, 32, seed=61, kind=1, quality=95, ri=2, tables=tables),
+              synth.make_jpeg(160, 32, seed=62, kind=0, quality=85, ri=3, tables=tables, qtables=(1, 0, 0))]
+    frames += [_flipped(frames[0], rng, int(rng.integers(1, 10))) for _ in range(2)]
+    for j in frames:
+        try:
+            want = orc.ImageData(j).decode()
+        except orc.OracleError:
+            continue
+        for fused in (1, 7):   # the fused kernel; its streamed window
+            got = _run(runner, tmp_path, j, fused, window=2048 if fused == 1 else 5)
+            assert np.array_equal(got, want), (name, fused, int((got != want).any(axis=2).sum()))
+        for passes in (4, 1):
+            got = _run(runner, tmp_path, j, 5, window=0, coop_passes=passes)
+            assert got is not None and np.array_equal(got, want), (name, "coop", passes)
+        for rows, below, chunk in ((64, 24, 1), (9, 4, 1), (3, 1, 1), (64, 30, 3)):
+            got = _run(runner, tmp_path, j, 8, window=rows, below=below, chunk=chunk)
+            if name == "three_pairs":
+                assert got is None   # (mcu_ok: more pairs than the walk tables hold)
+                continue
+            assert got is not None and np.array_equal(got, want), (name, rows, below, chunk)
+    # the cooperative kernel at longer restart intervals (through the walk tables up to 40 MCUs, speculative beyond)
+    for ri in (4, 30, 120):
+        j = synth.make_jpeg(480, 32 if ri < 120 else 64, seed=63 + ri, kind=0, quality=90, ri=ri, tables=tables)
+        want = orc.ImageData(j).decode()
+        got = _run(runner, tmp_path, j, 5, window=0, coop_passes=4)
+        assert got is not None and np.array_equal(got, want), (name, ri)
+        got = _run(runner, tmp_path, j, 8, window=40, below=20, chunk=2)
+        assert (got is None) if name == "three_pairs" else np.array_equal(got, want), (name, ri)
+    # standard entropy
+    j = frames[1]
+    want = orc.ImageData(j, standard_entropy=True).decode()
+    for fused in (1, 5, 8):
+        got = _run(runner, tmp_path, j, fused, window=40 if fused == 8 else 2048, standard=True)
+        if got is not None or name != "three_pairs":
+            assert np.array_equal(got, want), (name, "standard", fused)
+
+
+@pytest.mark.parametrize("sampling", [(1, 1), (1, 2), (2, 2)])
+def test_emulated_extension_layouts_any_table_selectors(runner, tmp_path, sampling):
+    """The extension layouts' kernels (fused, streamed, entropy records) with every selector set."""
+    for k, (name, tables) in enumerate(sorted(synth.SELECTOR_SETS.items())):
+        jpeg = synth.make_jpeg(96, 32, seed=70 + k, kind=k % 2, quality=90, ri=2 + k % 2, sampling=sampling, tables=tables)
+        want = orc.ImageData(jpeg, allow_sampling=True).decode()
+        got = _run(runner, tmp_path, jpeg, 4)
+        assert np.array_equal(got, want), (sampling, name, "records")
+        got = _run(runner, tmp_path, jpeg, 6, waves=3, window=300)
+        assert np.array_equal(got, want), (sampling, name, "fused")
+        got = _run(runner, tmp_path, jpeg, 6, waves=2, layout_rows=6, stage=0xf, below=3)
+        assert np.array_equal(got, want), (sampling, name, "streamed")
+
+
 def test_emulated_rare_paths_were_reached():
     """Runs last in this module: the cases above must have exercised every branch of the fast
     entropy path (counters come from the emulator build, -DCG_EMUL_STATS)."""

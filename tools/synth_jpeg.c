@@ -140,6 +140,23 @@ static int bit_size(int v)
     return n;
 }
 
+/* SJ_NO_ZRL: a coefficient behind 16 or more zeros would need a ZRL code -- it is quantised to zero (and so is
+ * every later one: the run only grows) */
+static void drop_after_long_runs(int16_t zz[64])
+{
+    int run = 0;
+    for (int k = 1; k < 64; k++) {
+        if (zz[k] == 0) {
+            run++;
+            continue;
+        }
+        if (run > 15)
+            zz[k] = 0;
+        else
+            run = 0;
+    }
+}
+
 static void encode_block(bitw *w, const int16_t zz[64], int *pred, const enc_table *dc,
                          const enc_table *ac)
 {
@@ -219,14 +236,50 @@ static void scale_qtable(const uint8_t base[64], int quality, uint8_t out_zz[64]
 #define SJ_NO_DHT 1u      /* omit DHT segments (decoder must fall back to Annex K) */
 #define SJ_NO_EOI 2u      /* truncate before EOI */
 #define SJ_JFIF 4u        /* emit a JFIF APP0 header */
+#define SJ_NO_ZRL 8u      /* both AC tables without the ZRL symbol (0xF0); coefficients behind a run of 16 zeros are dropped */
 
 /*
  * rgb: h*w*3 bytes.  hs,vs: luma sampling factors.  ri: MCUs per restart
  * interval (0 = no DRI).  Returns the number of bytes needed; the stream is
  * complete only when the return value <= cap.
  */
+size_t synth_encode_sel(const uint8_t *rgb, int w, int h, int quality, int hs, int vs, int ri,
+                        unsigned flags, const int sel[9], uint8_t *out, size_t cap);
+
 size_t synth_encode(const uint8_t *rgb, int w, int h, int quality, int hs, int vs, int ri,
                     unsigned flags, uint8_t *out, size_t cap)
+{
+    static const int dflt[9] = {0, 0, 0, 1, 1, 1, 1, 1, 1};
+    return synth_encode_sel(rgb, w, h, quality, hs, vs, ri, flags, dflt, out, cap);
+}
+
+/* Drops symbol `sym` from a table (bits, vals -> out_bits, out_vals); returns the new symbol count. */
+static int drop_symbol(const uint8_t bits[16], const uint8_t *vals, int nval, uint8_t sym, uint8_t out_bits[16],
+                       uint8_t *out_vals)
+{
+    int k = 0, m = 0;
+    for (int l = 0; l < 16; l++) {
+        out_bits[l] = bits[l];
+        for (int i = 0; i < bits[l]; i++, k++) {
+            if (k < nval && vals[k] == sym)
+                out_bits[l]--;
+            else if (k < nval)
+                out_vals[m++] = vals[k];
+        }
+    }
+    return m;
+}
+
+/*
+ * As synth_encode, with the tables every component is coded with chosen:
+ * sel[3 c + 0] = Td (DC Huffman table), sel[3 c + 1] = Ta (AC Huffman table),
+ * sel[3 c + 2] = Tq (quantisation table) of component c (Y, Cb, Cr), each 0
+ * or 1.  Table 0 is the Annex K luma table, table 1 the chroma one; the DQT
+ * and DHT segments are the same whatever the selectors (synth_encode: Y on
+ * 0/0/0, Cb and Cr on 1/1/1).
+ */
+size_t synth_encode_sel(const uint8_t *rgb, int w, int h, int quality, int hs, int vs, int ri,
+                        unsigned flags, const int sel[9], uint8_t *out, size_t cap)
 {
     uint8_t ql[64], qc[64];
     float rql[64], rqc[64];
@@ -238,11 +291,29 @@ size_t synth_encode(const uint8_t *rgb, int w, int h, int quality, int hs, int v
     }
     if (!cos_ready)
         init_cos();
-    enc_table dcl, dcc, acl, acc;
-    make_enc_table(&dcl, DC_L_BITS, DC_VALS);
-    make_enc_table(&dcc, DC_C_BITS, DC_VALS);
-    make_enc_table(&acl, AC_L_BITS, AC_L_VALS);
-    make_enc_table(&acc, AC_C_BITS, AC_C_VALS);
+    uint8_t acl_bits[16], acc_bits[16], acl_vals[162], acc_vals[162];
+    int nacl = 162, nacc = 162;
+    if (flags & SJ_NO_ZRL) {
+        nacl = drop_symbol(AC_L_BITS, AC_L_VALS, 162, 0xf0, acl_bits, acl_vals);
+        nacc = drop_symbol(AC_C_BITS, AC_C_VALS, 162, 0xf0, acc_bits, acc_vals);
+    } else {
+        memcpy(acl_bits, AC_L_BITS, 16);
+        memcpy(acc_bits, AC_C_BITS, 16);
+        memcpy(acl_vals, AC_L_VALS, 162);
+        memcpy(acc_vals, AC_C_VALS, 162);
+    }
+    enc_table dct[2], act[2];
+    make_enc_table(&dct[0], DC_L_BITS, DC_VALS);
+    make_enc_table(&dct[1], DC_C_BITS, DC_VALS);
+    make_enc_table(&act[0], acl_bits, acl_vals);
+    make_enc_table(&act[1], acc_bits, acc_vals);
+    const float *rq[2] = {rql, rqc};
+    int td[3], ta[3], tq[3];
+    for (int c = 0; c < 3; c++) {
+        td[c] = sel[3 * c] & 1;
+        ta[c] = sel[3 * c + 1] & 1;
+        tq[c] = sel[3 * c + 2] & 1;
+    }
 
     bitw W = {out, cap, 0, 0, 0, 0};
     bitw *bw = &W;
@@ -274,17 +345,17 @@ size_t synth_encode(const uint8_t *rgb, int w, int h, int quality, int hs, int v
     put_byte(bw, 3);
     put_byte(bw, 1);
     put_byte(bw, (uint8_t)(hs << 4 | vs));
-    put_byte(bw, 0);
+    put_byte(bw, (uint8_t)tq[0]);
     put_byte(bw, 2);
     put_byte(bw, 0x11);
-    put_byte(bw, 1);
+    put_byte(bw, (uint8_t)tq[1]);
     put_byte(bw, 3);
     put_byte(bw, 0x11);
-    put_byte(bw, 1);
+    put_byte(bw, (uint8_t)tq[2]);
     if (!(flags & SJ_NO_DHT)) {
-        const uint8_t *bits[4] = {DC_L_BITS, AC_L_BITS, DC_C_BITS, AC_C_BITS};
-        const uint8_t *vals[4] = {DC_VALS, AC_L_VALS, DC_VALS, AC_C_VALS};
-        const int nval[4] = {12, 162, 12, 162};
+        const uint8_t *bits[4] = {DC_L_BITS, acl_bits, DC_C_BITS, acc_bits};
+        const uint8_t *vals[4] = {DC_VALS, acl_vals, DC_VALS, acc_vals};
+        const int nval[4] = {12, nacl, 12, nacc};
         const uint8_t tcth[4] = {0x00, 0x10, 0x01, 0x11};
         for (int t = 0; t < 4; t++) {
             put_marker(bw, 0xc4);
@@ -299,12 +370,10 @@ size_t synth_encode(const uint8_t *rgb, int w, int h, int quality, int hs, int v
     put_marker(bw, 0xda);
     put_u16(bw, 12);
     put_byte(bw, 3);
-    put_byte(bw, 1);
-    put_byte(bw, 0x00);
-    put_byte(bw, 2);
-    put_byte(bw, 0x11);
-    put_byte(bw, 3);
-    put_byte(bw, 0x11);
+    for (int c = 0; c < 3; c++) {
+        put_byte(bw, (uint8_t)(c + 1));
+        put_byte(bw, (uint8_t)(td[c] << 4 | ta[c]));
+    }
     put_byte(bw, 0);
     put_byte(bw, 63);
     put_byte(bw, 0);
@@ -348,8 +417,10 @@ size_t synth_encode(const uint8_t *rgb, int w, int h, int quality, int hs, int v
                     for (int y = 0; y < 8; y++)
                         for (int x = 0; x < 8; x++)
                             blk[y * 8 + x] = Y[(v * 8 + y) * mw + u * 8 + x];
-                    fdct_quant(blk, rql, zz);
-                    encode_block(bw, zz, &pred[0], &dcl, &acl);
+                    fdct_quant(blk, rq[tq[0]], zz);
+                    if (flags & SJ_NO_ZRL)
+                        drop_after_long_runs(zz);
+                    encode_block(bw, zz, &pred[0], &dct[td[0]], &act[ta[0]]);
                 }
             for (int c = 0; c < 2; c++) {
                 const float *src = c ? Cr : Cb;
@@ -361,8 +432,10 @@ size_t synth_encode(const uint8_t *rgb, int w, int h, int quality, int hs, int v
                                 s += src[(y * vs + dy) * mw + x * hs + dx];
                         blk[y * 8 + x] = s / (float)(hs * vs);
                     }
-                fdct_quant(blk, rqc, zz);
-                encode_block(bw, zz, &pred[1 + c], &dcc, &acc);
+                fdct_quant(blk, rq[tq[1 + c]], zz);
+                if (flags & SJ_NO_ZRL)
+                    drop_after_long_runs(zz);
+                encode_block(bw, zz, &pred[1 + c], &dct[td[1 + c]], &act[ta[1 + c]]);
             }
         }
     }
