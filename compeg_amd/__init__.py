@@ -18,10 +18,10 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
-                   LIB_PATH, METADATA_BYTES, Error, check, lib)
+                   LIB_PATH, METADATA_BYTES, Error, TensorSpec, check, lib)
 
 __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Texture", "Error", "HostBuffer", "JpegList",
-           "host_register", "host_unregister", "version", "LIB_PATH"]
+           "host_register", "host_unregister", "version", "LIB_PATH", "tensor_shape", "TENSOR_DTYPES", "TENSOR_ORDERS"]
 
 
 # compeg_decoder_last_kernel / compeg_batch_last_kernel (include/compeg_hip.h: COMPEG_KERNEL_*)
@@ -30,6 +30,55 @@ KERNEL_NAMES = ("none", "fused", "pair", "coop_team", "generic", "split", "fused
 
 def version():
     return lib.compeg_version().decode()
+
+
+# Tensor output (include/compeg_hip.h: COMPEG_TENSOR_*): element types and plane orders by name
+TENSOR_DTYPES = {"u8": 0, "f16": 1, "bf16": 2, "f32": 3}
+TENSOR_ORDERS = {"rgb": 0, "bgr": 1}
+
+
+def _tensor_spec(dtype, downscale, scale, bias, order):
+    """compeg_tensor_spec from names (or the header's numbers, which the library checks)."""
+    spec = TensorSpec()
+    if isinstance(dtype, str) and dtype not in TENSOR_DTYPES:
+        raise Error(f"unknown tensor dtype {dtype!r} (one of {', '.join(TENSOR_DTYPES)})")
+    if isinstance(order, str) and order not in TENSOR_ORDERS:
+        raise Error(f"unknown tensor order {order!r} (one of {', '.join(TENSOR_ORDERS)})")
+    spec.dtype = TENSOR_DTYPES[dtype] if isinstance(dtype, str) else dtype
+    spec.order = TENSOR_ORDERS[order] if isinstance(order, str) else order
+    spec.downscale, spec.reserved = downscale, 0
+    spec.scale[:] = [float(x) for x in scale]
+    spec.bias[:] = [float(x) for x in bias]
+    return spec
+
+
+def tensor_shape(width, height, dtype="f16", downscale=1):
+    """((3, oh, ow), bytes) of one WxH image's tensor (compeg_tensor_shape; no device needed)."""
+    spec = _tensor_spec(dtype, downscale, (1, 1, 1), (0, 0, 0), "rgb")
+    ow, oh, nbytes = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    check(lib.compeg_tensor_shape(C.byref(spec), width, height, C.byref(ow), C.byref(oh), C.byref(nbytes)))
+    return (3, oh.value, ow.value), nbytes.value
+
+
+def _device_range(dst):
+    """(address, bytes) of a pack destination: such a pair; a tensor-like object (data_ptr / numel / element_size);
+    or anything with __cuda_array_interface__ (contiguous).  No framework is imported for it."""
+    if isinstance(dst, tuple) and len(dst) == 2:
+        return int(dst[0]), int(dst[1])
+    if hasattr(dst, "data_ptr") and hasattr(dst, "numel") and hasattr(dst, "element_size"):
+        if hasattr(dst, "is_contiguous") and not dst.is_contiguous():
+            raise Error("pack_tensor: the destination must be contiguous")
+        return int(dst.data_ptr()), int(dst.numel()) * int(dst.element_size())
+    cai = getattr(dst, "__cuda_array_interface__", None)
+    if cai is not None:
+        itemsize = np.dtype(cai["typestr"]).itemsize
+        shape = tuple(cai["shape"])
+        strides = cai.get("strides")
+        tight = tuple(int(np.prod(shape[i + 1:], dtype=np.int64)) * itemsize for i in range(len(shape)))
+        if strides is not None and tuple(strides) != tight:
+            raise Error("pack_tensor: the destination must be contiguous")
+        return int(cai["data"][0]), int(np.prod(shape, dtype=np.int64)) * itemsize
+    raise Error("pack_tensor: dst is neither (address, nbytes), a tensor, nor a __cuda_array_interface__ object")
 
 
 def _host_view(data):
@@ -331,6 +380,16 @@ class Decoder:
         check(lib.compeg_decoder_read_output(self._h, out.ctypes.data, width, height))
         return out
 
+    def pack_tensor(self, dst, dtype="f16", downscale=1, scale=(1, 1, 1), bias=(0, 0, 0), order="rgb", hip_stream=0):
+        """Extension (compeg_decoder_pack_tensor): records, on hip_stream (0 = the gpu's stream), the pack of the last decoded image into
+        caller-owned device memory as the planar tensor a model reads -- [3, H / downscale, W / downscale], alpha dropped, block mean over
+        downscale x downscale pixels, then * scale[c] + bias[c] per plane, stored as dtype ("u8", "f16", "bf16", "f32").
+        dst: (address, nbytes), a tensor (data_ptr / numel / element_size), or a __cuda_array_interface__ object.
+        Returns without waiting; the pack runs behind the decode and the next decode behind the pack."""
+        spec = _tensor_spec(dtype, downscale, scale, bias, order)
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_decoder_pack_tensor(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
+
     def read_coefficients(self, total_dus):
         out = np.empty(total_dus * 32, dtype=np.int32)
         check(lib.compeg_decoder_read_coefficients(self._h, out.ctypes.data, out.size))
@@ -406,6 +465,16 @@ class Batch:
         out = np.empty((t.height, t.width, 4), dtype=np.uint8)
         check(lib.compeg_batch_read_output(self._h, index, out.ctypes.data))
         return out
+
+    def pack_tensor(self, dst, dtype="f16", downscale=1, scale=(1, 1, 1), bias=(0, 0, 0), order="rgb", hip_stream=0):
+        """Extension (compeg_batch_pack_tensor): records, on hip_stream (0 = the gpu's stream), the pack of the last decode's images (all of one size) into
+        caller-owned device memory as the planar tensor a model reads -- [count, 3, H / downscale, W / downscale], alpha dropped, block mean over
+        downscale x downscale pixels, then * scale[c] + bias[c] per plane, stored as dtype ("u8", "f16", "bf16", "f32").
+        dst: (address, nbytes), a tensor (data_ptr / numel / element_size), or a __cuda_array_interface__ object.
+        Returns without waiting; the pack runs behind the decode and the next decode behind the pack."""
+        spec = _tensor_spec(dtype, downscale, scale, bias, order)
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_batch_pack_tensor(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
 
     def algorithmic_bytes(self):
         return lib.compeg_batch_algorithmic_bytes(self._h)

@@ -22,6 +22,12 @@ class Error(Exception):
         self.code = code
 
 
+class TensorSpec(C.Structure):
+    """compeg_tensor_spec (include/compeg_hip.h, "Tensor output")."""
+    _fields_ = [("dtype", C.c_uint32), ("order", C.c_uint32), ("downscale", C.c_uint32), ("reserved", C.c_uint32),
+                ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -98,6 +104,9 @@ def _load():
         "compeg_host_register": (i, [vp, C.c_size_t]),
         "compeg_host_unregister": (i, [vp]),
         "compeg_decoder_last_kernel": (i, [vp]),
+        "compeg_tensor_shape": (i, [C.POINTER(TensorSpec), u32, u32, pu32, pu32, psz]),
+        "compeg_decoder_pack_tensor": (i, [vp, C.POINTER(TensorSpec), vp, sz, vp]),
+        "compeg_batch_pack_tensor": (i, [vp, C.POINTER(TensorSpec), vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("COMPEG_LIB") and not hasattr(L, name):

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -104,6 +105,57 @@ int open_gpu(int device, hipStream_t stream, bool adopt, compeg_gpu **out)
     }
     *out = g;
     return ok();
+}
+
+// compeg_tensor_spec as the header has it: 0 with the element size, or the error recorded.  (The texts name values,
+// not the header's macros.)
+int check_tensor_spec(const compeg_tensor_spec *spec, size_t *elem_bytes)
+{
+    if (!spec)
+        return fail(COMPEG_E_INVALID_ARG, "spec is NULL");
+    if (spec->dtype > COMPEG_TENSOR_F32)
+        return fail(COMPEG_E_INVALID_ARG, ("tensor spec: dtype " + std::to_string(spec->dtype) + " is none of 0 (u8), 1 (f16), 2 (bf16), 3 (f32)").c_str());
+    if (spec->order > COMPEG_TENSOR_BGR)
+        return fail(COMPEG_E_INVALID_ARG, ("tensor spec: order " + std::to_string(spec->order) + " is neither 0 (rgb) nor 1 (bgr)").c_str());
+    const uint32_t k = spec->downscale;
+    if (k != 1u && k != 2u && k != 4u && k != 8u)
+        return fail(COMPEG_E_INVALID_ARG, ("tensor spec: downscale " + std::to_string(k) + " is none of 1, 2, 4, 8").c_str());
+    if (spec->reserved != 0u)
+        return fail(COMPEG_E_INVALID_ARG, "tensor spec: reserved must be 0");
+    for (int c = 0; c < 3; c++)
+        if (!std::isfinite(spec->scale[c]) || !std::isfinite(spec->bias[c]))
+            return fail(COMPEG_E_INVALID_ARG, ("tensor spec: scale or bias of plane " + std::to_string(c) + " is not finite").c_str());
+    *elem_bytes = spec->dtype == COMPEG_TENSOR_U8 ? 1u : (spec->dtype == COMPEG_TENSOR_F32 ? 4u : 2u);
+    return COMPEG_OK;
+}
+
+// ... and the geometry of one image's tensor; every count in size_t
+int tensor_geometry(const compeg_tensor_spec *spec, uint32_t width, uint32_t height, uint32_t *ow, uint32_t *oh, size_t *bytes,
+                    size_t *elem_bytes)
+{
+    const int rc = check_tensor_spec(spec, elem_bytes);
+    if (rc != COMPEG_OK)
+        return rc;
+    const uint32_t k = spec->downscale;
+    if (width < k || height < k)
+        return fail(COMPEG_E_INVALID_ARG, ("tensor: a " + std::to_string(width) + "x" + std::to_string(height) + " image is smaller than the downscale factor " +
+                                           std::to_string(k)).c_str());
+    *ow = width / k;
+    *oh = height / k;
+    *bytes = size_t(3) * size_t(*oh) * size_t(*ow) * *elem_bytes;
+    return COMPEG_OK;
+}
+
+// What both pack calls ask of the destination.
+int check_tensor_destination(const void *device_dst, size_t dst_bytes, size_t needed, size_t elem_bytes)
+{
+    if (!device_dst)
+        return fail(COMPEG_E_INVALID_ARG, "device_dst is NULL");
+    if (reinterpret_cast<uintptr_t>(device_dst) % elem_bytes != 0)
+        return fail(COMPEG_E_INVALID_ARG, ("tensor: device_dst is not aligned to its element size of " + std::to_string(elem_bytes) + " bytes").c_str());
+    if (dst_bytes < needed)
+        return fail(COMPEG_E_INVALID_ARG, ("tensor: dst_bytes is " + std::to_string(dst_bytes) + ", the tensor needs " + std::to_string(needed)).c_str());
+    return COMPEG_OK;
 }
 
 } // namespace
@@ -925,6 +977,82 @@ int compeg_batch_timing(compeg_batch *batch, int reset, uint32_t *decodes, doubl
         if (reset)
             batch->decodes_timed = 0;
         return ok();
+    });
+}
+
+/* ---- Tensor output -------------------------------------------------------- */
+
+int compeg_tensor_shape(const compeg_tensor_spec *spec, uint32_t width, uint32_t height, uint32_t *out_width,
+                        uint32_t *out_height, size_t *bytes_per_image)
+{
+    return guarded([&] {
+        uint32_t ow = 0, oh = 0;
+        size_t bytes = 0, elem = 0;
+        const int rc = tensor_geometry(spec, width, height, &ow, &oh, &bytes, &elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (out_width)
+            *out_width = ow;
+        if (out_height)
+            *out_height = oh;
+        if (bytes_per_image)
+            *bytes_per_image = bytes;
+        return ok();
+    });
+}
+
+int compeg_decoder_pack_tensor(compeg_decoder *dec, const compeg_tensor_spec *spec, void *device_dst, size_t dst_bytes,
+                               void *hip_stream)
+{
+    return guarded([&] {
+        if (!dec)
+            return fail(COMPEG_E_INVALID_ARG, "dec is NULL");
+        size_t elem = 0;
+        int rc = check_tensor_spec(spec, &elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (!dec->have_last || !dec->out.ptr)
+            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
+        // (the texture never shrinks: the last image's own extent, at the allocation's pitch)
+        uint32_t ow = 0, oh = 0;
+        size_t bytes = 0;
+        rc = tensor_geometry(spec, dec->last_w, dec->last_h, &ow, &oh, &bytes, &elem);
+        if (rc == COMPEG_OK)
+            rc = check_tensor_destination(device_dst, dst_bytes, bytes, elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        Status s = dec->pack_tensor(*spec, device_dst, hip_stream ? static_cast<hipStream_t>(hip_stream) : dec->gpu->stream);
+        return s.ok() ? ok() : fail(s);
+    });
+}
+
+int compeg_batch_pack_tensor(compeg_batch *batch, const compeg_tensor_spec *spec, void *device_dst, size_t dst_bytes,
+                             void *hip_stream)
+{
+    return guarded([&] {
+        if (!batch)
+            return fail(COMPEG_E_INVALID_ARG, "batch is NULL");
+        size_t elem = 0;
+        int rc = check_tensor_spec(spec, &elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (!batch->count || !batch->output_decoded)
+            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
+        const ImageDesc &first = batch->descs[0];
+        for (size_t i = 1; i < batch->count; i++)
+            if (batch->descs[i].out_w != first.out_w || batch->descs[i].out_h != first.out_h)
+                return fail(COMPEG_E_INVALID_ARG, ("tensor: the batch's images are not all of one size (image " + std::to_string(i) + " is " +
+                                                   std::to_string(batch->descs[i].out_w) + "x" + std::to_string(batch->descs[i].out_h) + ", image 0 " +
+                                                   std::to_string(first.out_w) + "x" + std::to_string(first.out_h) + ")").c_str());
+        uint32_t ow = 0, oh = 0;
+        size_t bytes = 0;
+        rc = tensor_geometry(spec, first.out_w, first.out_h, &ow, &oh, &bytes, &elem);
+        if (rc == COMPEG_OK)
+            rc = check_tensor_destination(device_dst, dst_bytes, bytes * batch->count, elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        Status s = batch->pack_tensor(*spec, device_dst, hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream);
+        return s.ok() ? ok() : fail(s);
     });
 }
 

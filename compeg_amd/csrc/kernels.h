@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "compeg_hip.h"
 #include "device_types.h"
 
 namespace compeg {
@@ -104,6 +105,11 @@ hipError_t launch_entropy_samples(const ImageDesc *descs, uint32_t images, uint3
                                   const HuffLdsPlan &plan, hipStream_t stream);
 hipError_t launch_generic_composite(const ImageDesc *descs, uint32_t images, uint32_t max_w, uint32_t max_h,
                                     hipStream_t stream);
+
+// Tensor output (tensor_kernels.hip, tensor_body.h): packs the WxH corner of `images` RGBA8 outputs, src_image_stride
+// bytes apart with rows of src_pitch bytes, into [images][3][H / k][W / k] at dst, tight.  spec: validated by the caller.
+hipError_t launch_pack_tensor(const void *src, size_t src_image_stride, uint32_t src_pitch, uint32_t width, uint32_t height,
+                              uint32_t images, const compeg_tensor_spec &spec, void *dst, hipStream_t stream);
 
 #if defined(CG_AC_STAMPS)
 // diagnostic build: AC-loop cycle counters (kernels_body.h)

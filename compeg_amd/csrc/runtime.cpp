@@ -788,6 +788,8 @@ Status compeg_decoder::enqueue(const ImageData &img, hipStream_t stream, bool *c
     }
     last_stream = stream;
     last_md = md;
+    last_w = img.width;
+    last_h = img.height;
     last_desc_dev = db;
     have_last = true;
 
@@ -1216,6 +1218,7 @@ Status compeg_batch::upload_host(size_t n, int threads, const void *items_, cons
     // soon as it is done -- the transfers run under the preprocessing of the images that follow.
     descs.assign(n, ImageDesc{});
     out_offset.assign(n, 0);
+    output_decoded = false;
     std::vector<size_t> in_off(n);
     size_t in_total = 0, ac_total = 0, dc_total = 0, out_total = 0;
     bool any_generic = false;
@@ -1886,6 +1889,7 @@ Status compeg_batch::upload_device_scan(size_t n, int threads, const FeedSource 
 
         descs.assign(n, ImageDesc{});
         out_offset.assign(n, 0);
+        output_decoded = false;
         host_fallbacks = 0;
         size_t out_at = 0, ac_at = 0, dc_at = 0;
         for (size_t i = 0; i < n; i++) {
@@ -2239,6 +2243,45 @@ Status compeg_batch::decode(hipStream_t stream)
         decodes_timed++;
     }
     decode_recorded = true;
+    output_decoded = true;
+    last_stream = stream;
+    return Status{};
+}
+
+// Tensor output.  Both packs read `out` on a stream of the caller's choice: behind the last decode (the scheme of
+// compeg_batch::decode for decodes on different streams), and whatever touches `out` next -- a decode, an upload, a
+// read-back: they all order themselves behind last_stream -- behind the pack.
+Status compeg_decoder::pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream)
+{
+    CG_HIP(hipSetDevice(gpu->device));
+    if (!decode_done)
+        CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
+    if (decode_pending && stream != last_stream)
+        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
+    CG_HIP(launch_pack_tensor(out.ptr, 0, uint32_t(out_pitch), last_w, last_h, 1, spec, dst, stream));
+    // (enqueue on another stream waits for this event: now it stands behind the pack as well)
+    CG_HIP(hipEventRecord(decode_done, stream));
+    decode_pending = true;
+    last_stream = stream;
+    return Status{};
+}
+
+Status compeg_batch::pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream)
+{
+    CG_HIP(hipSetDevice(gpu->device));
+    if (decode_recorded && stream != last_stream) {
+        if (!decode_done)
+            CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
+        CG_HIP(hipEventRecord(decode_done, last_stream));
+        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
+    }
+    // images of one size lie one stride apart (upload: out_offset)
+    const size_t stride = count > 1 ? out_offset[1] - out_offset[0] : 0;
+    for (size_t i = 0; i < count; i++)
+        if (descs[i].out != static_cast<uint8_t *>(out.ptr) + out_offset[0] + i * stride || descs[i].out_pitch != descs[0].out_pitch)
+            return Status::error(COMPEG_E_INVALID_ARG, "tensor: the batch's outputs are not evenly spaced");
+    CG_HIP(launch_pack_tensor(descs[0].out, stride, descs[0].out_pitch, descs[0].out_w, descs[0].out_h, uint32_t(count), spec, dst, stream));
+    // (no timing events; the next decode on another stream records decode_done on last_stream, behind this)
     last_stream = stream;
     return Status{};
 }

@@ -97,6 +97,7 @@ struct compeg_decoder {
     // what read_coefficients needs to rebuild the reference's buffer
     compeg::Metadata last_md{};
     bool have_last = false;
+    uint32_t last_w = 0, last_h = 0; // the last image's own extent (out_w x out_h never shrink)
     compeg::HuffLdsPlan last_plan{};
     uint32_t last_span = 0;
     bool coefficients_valid = false; // ac/dc hold the last image's coefficients
@@ -125,6 +126,9 @@ struct compeg_decoder {
     // may_defer: the caller will wait for the stream and then call finish_deferred(img)
     compeg::Status enqueue(const compeg::ImageData &img, hipStream_t stream, bool *changed, bool may_defer = false);
     compeg::Status finish_deferred(const compeg::ImageData &img, hipStream_t stream);
+    // Tensor output (compeg_hip.h): the last image's corner of `out`, packed on `stream` behind the last decode; the next
+    // decode waits for it.  spec and dst: checked by the caller.
+    compeg::Status pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream);
     compeg::Status check_scan_result(bool &fell_back);
     compeg::Status preprocess_on_device(const compeg::ImageData &img, hipStream_t stream, uint32_t &nwords,
                                         uint32_t &nstarts, uint32_t &span, bool &fell_back, size_t blob_bytes,
@@ -218,4 +222,7 @@ struct compeg_batch {
     unsigned feed_flags = 0;
     std::vector<std::unique_ptr<compeg::ImageData>> feed_fresh;
     compeg::Status decode(hipStream_t stream);
+    bool output_decoded = false; // `out` holds a decode of the images uploaded last
+    // Tensor output (compeg_hip.h): every image's output (all of one size: checked by the caller, like spec and dst)
+    compeg::Status pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream);
 };

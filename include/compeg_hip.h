@@ -319,6 +319,49 @@ int compeg_batch_timing(compeg_batch *batch, int reset, uint32_t *decodes, doubl
 int compeg_batch_set_timing(compeg_batch *batch, int on);
 int compeg_batch_last_kernel(const compeg_batch *batch); /* COMPEG_KERNEL_* */
 
+/* ---- Tensor output (extension) -------------------------------
+ * The RGBA8 output above is the reference's wgpu::Texture, made for a viewer.  These calls pack the last decode of
+ * a decoder or a batch into what a model reads: planar, alpha dropped, optionally shrunk by an integer factor,
+ * converted and normalised -- one hand-written kernel in place of a chain of framework operations.  Nothing else
+ * changes: no existing call does, launches or reports anything different.
+ *
+ * Source: the object's RGBA8 output of its last decode; only the image's own WxH corner is used.
+ * k = downscale (1, 2, 4 or 8); ow = W / k, oh = H / k (rounded down; both at least 1).
+ * Plane c (0..2) takes source channel c (COMPEG_TENSOR_RGB) or 2 - c (COMPEG_TENSOR_BGR).  Output element (c, y, x):
+ *   s = integer sum of that channel over the k x k pixels at rows k*y .., columns k*x ..
+ *   m = float(s) * (1 / k^2)                 (exact in f32)
+ *   v = (m * scale[c]) + bias[c]             (two f32 operations, each rounded; never fused)
+ *   stored: v (F32); v rounded to nearest even (F16, BF16); rint(v), half to even, clamped to 0..255 (U8)
+ * so that k = 1, scale 1, bias 0, U8 gives the R, G and B planes byte for byte.  (The sign of a zero is not defined.)
+ * Destination: caller-owned device memory, contiguous, no padding: [3][oh][ow] for a decoder, [count][3][oh][ow]
+ * for a batch, aligned to its element size. */
+#define COMPEG_TENSOR_U8 0
+#define COMPEG_TENSOR_F16 1
+#define COMPEG_TENSOR_BF16 2
+#define COMPEG_TENSOR_F32 3
+#define COMPEG_TENSOR_RGB 0
+#define COMPEG_TENSOR_BGR 1
+typedef struct compeg_tensor_spec {
+    uint32_t dtype, order, downscale, reserved; /* COMPEG_TENSOR_*; reserved = 0 */
+    float scale[3];
+    float bias[3];
+} compeg_tensor_spec;
+/* No device needed: the geometry (each output optional) and the byte count of one image's tensor for a WxH source.
+ * COMPEG_E_INVALID_ARG for a spec the pack calls reject (values out of range, reserved != 0, a scale or bias that is not
+ * finite) and for W < k or H < k. */
+int compeg_tensor_shape(const compeg_tensor_spec *spec, uint32_t width, uint32_t height,
+                        uint32_t *out_width, uint32_t *out_height, size_t *bytes_per_image);
+/* Record the pack of the object's last decode on hip_stream (NULL = the gpu's stream) and return without waiting.
+ * The pack runs behind that decode whatever stream it was recorded on, and the object's next decode, upload or
+ * read-back runs behind the pack; compeg_batch_wait covers it.  It records none of the batch's timing events.  The
+ * decoder's texture never shrinks: the last image's WxH is packed.  COMPEG_E_INVALID_ARG also for: dst_bytes smaller
+ * than the tensor, device_dst not aligned to its element size, nothing decoded yet, a batch whose images are not
+ * all of one size. */
+int compeg_decoder_pack_tensor(compeg_decoder *dec, const compeg_tensor_spec *spec, void *device_dst,
+                               size_t dst_bytes, void *hip_stream);
+int compeg_batch_pack_tensor(compeg_batch *batch, const compeg_tensor_spec *spec, void *device_dst,
+                             size_t dst_bytes, void *hip_stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

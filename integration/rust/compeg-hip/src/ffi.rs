@@ -1,7 +1,7 @@
 //! Raw declarations of `include/compeg_hip.h`, one group per reference type.
 #![allow(non_camel_case_types)]
 
-use std::os::raw::{c_char, c_double, c_int, c_uint, c_void};
+use std::os::raw::{c_char, c_double, c_float, c_int, c_uint, c_void};
 
 macro_rules! opaque {
     ($($name:ident),*) => { $(#[repr(C)] pub struct $name { _private: [u8; 0] })* };
@@ -15,6 +15,18 @@ pub struct compeg_stage_times {
     pub preprocess_us: c_double,
     pub enqueue_writes_us: c_double,
     pub poll_us: c_double,
+}
+
+/// What `compeg_*_pack_tensor` makes of the RGBA8 output (compeg_hip.h, "Tensor output").
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct compeg_tensor_spec {
+    pub dtype: u32,
+    pub order: u32,
+    pub downscale: u32,
+    pub reserved: u32,
+    pub scale: [c_float; 3],
+    pub bias: [c_float; 3],
 }
 
 pub const COMPEG_OK: c_int = 0;
@@ -33,6 +45,13 @@ pub const COMPEG_KERNEL_GENERIC: c_int = 4;
 pub const COMPEG_KERNEL_SPLIT: c_int = 5;
 pub const COMPEG_KERNEL_FUSED_LAYOUT: c_int = 6;
 pub const COMPEG_KERNEL_FUSED_STREAM: c_int = 7;
+pub const COMPEG_KERNEL_WALK_MCU: c_int = 8;
+pub const COMPEG_TENSOR_U8: u32 = 0;
+pub const COMPEG_TENSOR_F16: u32 = 1;
+pub const COMPEG_TENSOR_BF16: u32 = 2;
+pub const COMPEG_TENSOR_F32: u32 = 3;
+pub const COMPEG_TENSOR_RGB: u32 = 0;
+pub const COMPEG_TENSOR_BGR: u32 = 1;
 
 extern "C" {
     pub fn compeg_last_error() -> *const c_char;
@@ -125,4 +144,12 @@ extern "C" {
     pub fn compeg_batch_timing(batch: *mut compeg_batch, reset: c_int, decodes: *mut u32, total_ms: *mut c_double,
                                stage_ms: *mut c_double) -> c_int;
     pub fn compeg_batch_last_kernel(batch: *const compeg_batch) -> c_int;
+
+    // Tensor output (extension)
+    pub fn compeg_tensor_shape(spec: *const compeg_tensor_spec, width: u32, height: u32, out_width: *mut u32,
+                               out_height: *mut u32, bytes_per_image: *mut usize) -> c_int;
+    pub fn compeg_decoder_pack_tensor(dec: *mut compeg_decoder, spec: *const compeg_tensor_spec, device_dst: *mut c_void,
+                                      dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_batch_pack_tensor(batch: *mut compeg_batch, spec: *const compeg_tensor_spec, device_dst: *mut c_void,
+                                    dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
 }

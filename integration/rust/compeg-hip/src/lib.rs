@@ -75,6 +75,51 @@ impl Stream {
     pub const DEFAULT: Stream = Stream(ptr::null_mut());
 }
 
+/// Element type of a packed tensor (`COMPEG_TENSOR_*`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum TensorType {
+    U8 = 0,
+    F16 = 1,
+    Bf16 = 2,
+    F32 = 3,
+}
+
+/// What `Decoder::pack_tensor` / `Batch::pack_tensor` make of the RGBA8 output (extension; compeg_hip.h, "Tensor
+/// output"): planes in RGB or BGR order, alpha dropped, the mean over `downscale` x `downscale` pixels (1, 2, 4 or 8),
+/// then `* scale[c] + bias[c]` per plane, stored as `dtype`.
+#[derive(Clone, Copy, Debug)]
+pub struct TensorSpec {
+    pub dtype: TensorType,
+    pub bgr: bool,
+    pub downscale: u32,
+    pub scale: [f32; 3],
+    pub bias: [f32; 3],
+}
+
+impl TensorSpec {
+    pub fn new(dtype: TensorType) -> Self {
+        TensorSpec { dtype, bgr: false, downscale: 1, scale: [1.0; 3], bias: [0.0; 3] }
+    }
+
+    fn raw(&self) -> ffi::compeg_tensor_spec {
+        ffi::compeg_tensor_spec {
+            dtype: self.dtype as u32,
+            order: if self.bgr { ffi::COMPEG_TENSOR_BGR } else { ffi::COMPEG_TENSOR_RGB },
+            downscale: self.downscale,
+            reserved: 0,
+            scale: self.scale,
+            bias: self.bias,
+        }
+    }
+
+    /// `(width, height, bytes)` of one `width` x `height` image's tensor; no device needed.
+    pub fn shape(&self, width: u32, height: u32) -> Result<(u32, u32, usize)> {
+        let (mut w, mut h, mut n) = (0, 0, 0);
+        check(unsafe { ffi::compeg_tensor_shape(&self.raw(), width, height, &mut w, &mut h, &mut n) })?;
+        Ok((w, h, n))
+    }
+}
+
 /// Device + stream + loaded gfx950 code object.  Immutable after creation and
 /// reference-counted inside the library; share it as `Arc<Gpu>` like the reference.
 pub struct Gpu {
@@ -307,6 +352,16 @@ impl Decoder {
         OwnedTexture { device_ptr: p, width: w, height: h, pitch_bytes: pitch }
     }
 
+    /// Extension: records on `stream` the pack of the last decoded image into `[3, h, w]` at `device_dst`
+    /// (caller-owned device memory of `dst_bytes` bytes) and returns without waiting; the pack runs behind the
+    /// decode, the next decode behind the pack.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn pack_tensor(&mut self, spec: &TensorSpec, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        check(ffi::compeg_decoder_pack_tensor(self.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
+    }
+
     /// Test helper (the reference's tests copy the texture to a buffer): waits and
     /// returns the image's `width x height` corner, tightly packed.
     pub fn read_output(&mut self, width: u32, height: u32) -> Result<Vec<u8>> {
@@ -453,6 +508,15 @@ impl Batch {
     /// Records the decode of every uploaded image on `stream` and returns without waiting.
     pub fn decode(&mut self, stream: Stream) -> Result<()> {
         check(unsafe { ffi::compeg_batch_decode(self.raw.as_ptr(), stream.0) })
+    }
+
+    /// Records on `stream` the pack of the last decode's images (all of one size) into `[len, 3, h, w]` at
+    /// `device_dst`; `wait` covers it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn pack_tensor(&mut self, spec: &TensorSpec, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        check(ffi::compeg_batch_pack_tensor(self.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
     }
 
     pub fn wait(&mut self) -> Result<()> {
