@@ -18,10 +18,11 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
-                   LIB_PATH, METADATA_BYTES, Error, TensorSpec, check, lib)
+                   LIB_PATH, METADATA_BYTES, Error, Rect, ResizeSpec, TensorSpec, check, lib)
 
 __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Texture", "Error", "HostBuffer", "JpegList",
-           "host_register", "host_unregister", "version", "LIB_PATH", "tensor_shape", "TENSOR_DTYPES", "TENSOR_ORDERS"]
+           "host_register", "host_unregister", "version", "LIB_PATH", "tensor_shape", "TENSOR_DTYPES", "TENSOR_ORDERS",
+           "resized_tensor_shape", "RESIZE_FILTERS", "ResizeSpec", "Rect"]
 
 
 # compeg_decoder_last_kernel / compeg_batch_last_kernel (include/compeg_hip.h: COMPEG_KERNEL_*)
@@ -58,6 +59,40 @@ def tensor_shape(width, height, dtype="f16", downscale=1):
     ow, oh, nbytes = C.c_uint32(), C.c_uint32(), C.c_size_t()
     check(lib.compeg_tensor_shape(C.byref(spec), width, height, C.byref(ow), C.byref(oh), C.byref(nbytes)))
     return (3, oh.value, ow.value), nbytes.value
+
+
+# Resized tensor output (include/compeg_hip.h: COMPEG_RESIZE_*): filters by name
+RESIZE_FILTERS = {"nearest": 0, "bilinear": 1}
+
+
+def _resize_spec(size, filter):
+    """compeg_resize_spec from size = (ow, oh) and a filter's name (or the header's number, which the library checks)."""
+    if isinstance(filter, str) and filter not in RESIZE_FILTERS:
+        raise Error(f"unknown resize filter {filter!r} (one of {', '.join(RESIZE_FILTERS)})")
+    ow, oh = size
+    spec = ResizeSpec()
+    spec.out_width, spec.out_height = ow, oh
+    spec.filter = RESIZE_FILTERS[filter] if isinstance(filter, str) else filter
+    spec.reserved = 0
+    return spec
+
+
+def _rect(crop):
+    x, y, w, h = crop
+    return Rect(x, y, w, h)
+
+
+def resized_tensor_shape(width, height, size, dtype="f16", downscale=1, filter="bilinear", crop=None):
+    """((3, oh, ow), bytes, (ph, pw)) of one WxH image's resized tensor: size = (ow, oh), crop = (x, y, w, h) or None for
+    the whole image, (ph, pw) the extent of the block-averaged crop that the filter reads (compeg_resized_tensor_shape;
+    no device needed)."""
+    spec = _tensor_spec(dtype, downscale, (1, 1, 1), (0, 0, 0), "rgb")
+    resize = _resize_spec(size, filter)
+    rect = _rect(crop) if crop is not None else None
+    pw, ph, nbytes = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    check(lib.compeg_resized_tensor_shape(C.byref(spec), C.byref(resize), width, height, C.byref(rect) if rect is not None else None,
+                                          C.byref(pw), C.byref(ph), C.byref(nbytes)))
+    return (3, resize.out_height, resize.out_width), nbytes.value, (ph.value, pw.value)
 
 
 def _device_range(dst):
@@ -390,6 +425,18 @@ class Decoder:
         addr, nbytes = _device_range(dst)
         check(lib.compeg_decoder_pack_tensor(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
 
+    def pack_tensor_resized(self, dst, size, crop=None, filter="bilinear", dtype="f16", downscale=1, scale=(1, 1, 1), bias=(0, 0, 0),
+                            order="rgb", hip_stream=0):
+        """Extension (compeg_decoder_pack_tensor_resized): like pack_tensor, but crop = (x, y, w, h) of the last decoded image (None: all
+        of it) is block-averaged over downscale x downscale pixels and then resized to size = (ow, oh) with filter ("bilinear":
+        half-pixel centres, no antialiasing; "nearest"), giving [3, oh, ow].  Returns without waiting."""
+        spec = _tensor_spec(dtype, downscale, scale, bias, order)
+        resize = _resize_spec(size, filter)
+        rect = _rect(crop) if crop is not None else None
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_decoder_pack_tensor_resized(self._h, C.byref(spec), C.byref(resize), C.byref(rect) if rect is not None else None,
+                                                     C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
+
     def read_coefficients(self, total_dus):
         out = np.empty(total_dus * 32, dtype=np.int32)
         check(lib.compeg_decoder_read_coefficients(self._h, out.ctypes.data, out.size))
@@ -475,6 +522,25 @@ class Batch:
         spec = _tensor_spec(dtype, downscale, scale, bias, order)
         addr, nbytes = _device_range(dst)
         check(lib.compeg_batch_pack_tensor(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
+
+    def pack_tensor_resized(self, dst, size, crops=None, filter="bilinear", dtype="f16", downscale=1, scale=(1, 1, 1), bias=(0, 0, 0),
+                            order="rgb", hip_stream=0):
+        """Extension (compeg_batch_pack_tensor_resized): the last decode's images, of whatever sizes, each block-averaged over downscale x
+        downscale pixels and resized to size = (ow, oh), giving [count, 3, oh, ow].  crops: None (whole images), one (x, y, w, h)
+        for every image, or a list with one per image.  Returns without waiting; wait() covers it."""
+        spec = _tensor_spec(dtype, downscale, scale, bias, order)
+        resize = _resize_spec(size, filter)
+        rects = None
+        if crops is not None:
+            n = self.count()
+            if len(crops) == 4 and not isinstance(crops[0], (tuple, list, Rect)):
+                crops = [crops] * n
+            if len(crops) != n:
+                raise Error(f"pack_tensor_resized: {len(crops)} crops for a batch of {n} images")
+            rects = (Rect * max(n, 1))(*[c if isinstance(c, Rect) else _rect(c) for c in crops])
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_batch_pack_tensor_resized(self._h, C.byref(spec), C.byref(resize), rects, C.c_void_p(addr), nbytes,
+                                                   C.c_void_p(hip_stream)))
 
     def algorithmic_bytes(self):
         return lib.compeg_batch_algorithmic_bytes(self._h)

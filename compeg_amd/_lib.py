@@ -28,6 +28,16 @@ class TensorSpec(C.Structure):
                 ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
 
 
+class ResizeSpec(C.Structure):
+    """compeg_resize_spec (include/compeg_hip.h, "Resized tensor output")."""
+    _fields_ = [("out_width", C.c_uint32), ("out_height", C.c_uint32), ("filter", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Rect(C.Structure):
+    """compeg_rect: a crop in pixels."""
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -107,6 +117,9 @@ def _load():
         "compeg_tensor_shape": (i, [C.POINTER(TensorSpec), u32, u32, pu32, pu32, psz]),
         "compeg_decoder_pack_tensor": (i, [vp, C.POINTER(TensorSpec), vp, sz, vp]),
         "compeg_batch_pack_tensor": (i, [vp, C.POINTER(TensorSpec), vp, sz, vp]),
+        "compeg_resized_tensor_shape": (i, [C.POINTER(TensorSpec), C.POINTER(ResizeSpec), u32, u32, C.POINTER(Rect), pu32, pu32, psz]),
+        "compeg_decoder_pack_tensor_resized": (i, [vp, C.POINTER(TensorSpec), C.POINTER(ResizeSpec), C.POINTER(Rect), vp, sz, vp]),
+        "compeg_batch_pack_tensor_resized": (i, [vp, C.POINTER(TensorSpec), C.POINTER(ResizeSpec), C.POINTER(Rect), vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("COMPEG_LIB") and not hasattr(L, name):

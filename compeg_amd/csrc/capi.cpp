@@ -158,6 +158,41 @@ int check_tensor_destination(const void *device_dst, size_t dst_bytes, size_t ne
     return COMPEG_OK;
 }
 
+// compeg_resize_spec as the header has it.
+int check_resize_spec(const compeg_resize_spec *resize)
+{
+    if (!resize)
+        return fail(COMPEG_E_INVALID_ARG, "resize is NULL");
+    if (resize->out_width == 0u || resize->out_height == 0u || resize->out_width > 65535u || resize->out_height > 65535u)
+        return fail(COMPEG_E_INVALID_ARG, ("resize: output size " + std::to_string(resize->out_width) + "x" + std::to_string(resize->out_height) +
+                                           " is not within 1..65535 both ways").c_str());
+    if (resize->filter > COMPEG_RESIZE_BILINEAR)
+        return fail(COMPEG_E_INVALID_ARG, ("resize: filter " + std::to_string(resize->filter) + " is neither 0 (nearest) nor 1 (bilinear)").c_str());
+    if (resize->reserved != 0u)
+        return fail(COMPEG_E_INVALID_ARG, "resize: reserved must be 0");
+    return COMPEG_OK;
+}
+
+// The crop of a WxH image (NULL: all of it) for downscale factor k, into `rect`; `which`: what the messages call the image.
+int check_crop(const compeg_rect *crop, uint32_t width, uint32_t height, uint32_t k, const std::string &which, compeg_rect *rect)
+{
+    const compeg_rect r = crop ? *crop : compeg_rect{0, 0, width, height};
+    const std::string text = std::to_string(r.width) + "x" + std::to_string(r.height);
+    if (crop) {
+        if (r.width == 0u || r.height == 0u)
+            return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "crop " + text + " has a side of 0").c_str());
+        // (64 bits: x + width must not wrap)
+        if (uint64_t(r.x) + r.width > width || uint64_t(r.y) + r.height > height)
+            return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "crop " + text + " at (" + std::to_string(r.x) + ", " + std::to_string(r.y) +
+                                               ") leaves the " + std::to_string(width) + "x" + std::to_string(height) + " image").c_str());
+    }
+    if (r.width < k || r.height < k)
+        return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + (crop ? "a " + text + " crop" : "a " + text + " image") +
+                                           " is smaller than the downscale factor " + std::to_string(k)).c_str());
+    *rect = r;
+    return COMPEG_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1052,6 +1087,86 @@ int compeg_batch_pack_tensor(compeg_batch *batch, const compeg_tensor_spec *spec
         if (rc != COMPEG_OK)
             return rc;
         Status s = batch->pack_tensor(*spec, device_dst, hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream);
+        return s.ok() ? ok() : fail(s);
+    });
+}
+
+/* ---- Resized tensor output ------------------------------------------------ */
+
+int compeg_resized_tensor_shape(const compeg_tensor_spec *spec, const compeg_resize_spec *resize, uint32_t width, uint32_t height,
+                                const compeg_rect *crop, uint32_t *pre_width, uint32_t *pre_height, size_t *bytes_per_image)
+{
+    return guarded([&] {
+        size_t elem = 0;
+        int rc = check_tensor_spec(spec, &elem);
+        if (rc == COMPEG_OK)
+            rc = check_resize_spec(resize);
+        compeg_rect r{};
+        if (rc == COMPEG_OK)
+            rc = check_crop(crop, width, height, spec->downscale, "", &r);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (pre_width)
+            *pre_width = r.width / spec->downscale;
+        if (pre_height)
+            *pre_height = r.height / spec->downscale;
+        if (bytes_per_image)
+            *bytes_per_image = size_t(3) * size_t(resize->out_height) * size_t(resize->out_width) * elem;
+        return ok();
+    });
+}
+
+int compeg_decoder_pack_tensor_resized(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_resize_spec *resize,
+                                       const compeg_rect *crop, void *device_dst, size_t dst_bytes, void *hip_stream)
+{
+    return guarded([&] {
+        if (!dec)
+            return fail(COMPEG_E_INVALID_ARG, "dec is NULL");
+        size_t elem = 0;
+        int rc = check_tensor_spec(spec, &elem);
+        if (rc == COMPEG_OK)
+            rc = check_resize_spec(resize);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (!dec->have_last || !dec->out.ptr)
+            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
+        // (the texture never shrinks: the last image's own extent, at the allocation's pitch)
+        compeg_rect r{};
+        rc = check_crop(crop, dec->last_w, dec->last_h, spec->downscale, "", &r);
+        if (rc == COMPEG_OK)
+            rc = check_tensor_destination(device_dst, dst_bytes, size_t(3) * size_t(resize->out_height) * size_t(resize->out_width) * elem, elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        Status s = dec->pack_tensor_resized(*spec, *resize, r, device_dst, hip_stream ? static_cast<hipStream_t>(hip_stream) : dec->gpu->stream);
+        return s.ok() ? ok() : fail(s);
+    });
+}
+
+int compeg_batch_pack_tensor_resized(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_resize_spec *resize,
+                                     const compeg_rect *crops, void *device_dst, size_t dst_bytes, void *hip_stream)
+{
+    return guarded([&] {
+        if (!batch)
+            return fail(COMPEG_E_INVALID_ARG, "batch is NULL");
+        size_t elem = 0;
+        int rc = check_tensor_spec(spec, &elem);
+        if (rc == COMPEG_OK)
+            rc = check_resize_spec(resize);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (!batch->count || !batch->output_decoded)
+            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
+        std::vector<compeg_rect> rects(batch->count);
+        for (size_t i = 0; i < batch->count; i++) {
+            rc = check_crop(crops ? crops + i : nullptr, batch->descs[i].out_w, batch->descs[i].out_h, spec->downscale,
+                            "image " + std::to_string(i) + ": ", &rects[i]);
+            if (rc != COMPEG_OK)
+                return rc;
+        }
+        rc = check_tensor_destination(device_dst, dst_bytes, size_t(3) * size_t(resize->out_height) * size_t(resize->out_width) * elem * batch->count, elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        Status s = batch->pack_tensor_resized(*spec, *resize, rects.data(), device_dst, hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream);
         return s.ok() ? ok() : fail(s);
     });
 }

@@ -111,6 +111,15 @@ hipError_t launch_generic_composite(const ImageDesc *descs, uint32_t images, uin
 hipError_t launch_pack_tensor(const void *src, size_t src_image_stride, uint32_t src_pitch, uint32_t width, uint32_t height,
                               uint32_t images, const compeg_tensor_spec &spec, void *dst, hipStream_t stream);
 
+// Resized tensor output (resize_kernels.hip, resize_body.h): `images` records (device memory, resize_body.h: ResizeImage)
+// into [images][3][oh][ow] at dst, tight.  Both specs: validated by the caller.
+constexpr size_t kResizeRecordBytes = 40;
+// ... and one image's record, written at `record` (kResizeRecordBytes bytes, 8-byte aligned): the crop of the image at
+// src, rows pitch bytes apart, for downscale factor k and an ow x oh output.  False: the crop is smaller than k.
+bool make_resize_record(void *record, const void *src, uint32_t pitch, const compeg_rect &crop, uint32_t k, uint32_t ow, uint32_t oh);
+hipError_t launch_resize_tensor(const void *device_records, uint32_t images, const compeg_tensor_spec &spec,
+                                const compeg_resize_spec &resize, void *dst, hipStream_t stream);
+
 #if defined(CG_AC_STAMPS)
 // diagnostic build: AC-loop cycle counters (kernels_body.h)
 hipError_t read_ac_stamps(unsigned long long out[4], bool reset);

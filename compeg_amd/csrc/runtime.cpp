@@ -94,6 +94,57 @@ Status PinnedBuffer::reserve(size_t bytes)
     return Status{};
 }
 
+RecordStage::~RecordStage()
+{
+    for (Slot &s : slots) {
+        if (s.copied)
+            (void)hipEventDestroy(s.copied);
+        if (s.host)
+            (void)hipHostFree(s.host);
+    }
+}
+
+Status RecordStage::upload(const void *records, size_t bytes, hipStream_t stream, const void **device_records)
+{
+    Slot *slot = nullptr;
+    for (Slot &s : slots) {
+        if (s.in_use) {
+            const hipError_t e = hipEventQuery(s.copied);
+            if (e == hipErrorNotReady) {
+                (void)hipGetLastError(); // (not an error: the copy has not run yet)
+                continue;
+            }
+            CG_HIP(e);
+            s.in_use = false;
+        }
+        slot = &s;
+        break;
+    }
+    if (!slot) {
+        slots.emplace_back();
+        slot = &slots.back();
+    }
+    if (!slot->copied)
+        CG_HIP(hipEventCreateWithFlags(&slot->copied, hipEventDisableTiming));
+    if (slot->capacity < bytes) {
+        if (slot->host) {
+            CG_HIP(hipHostFree(slot->host));
+            slot->host = nullptr;
+            slot->capacity = 0;
+        }
+        const size_t capacity = std::max<size_t>(bytes + bytes / 4, 4096);
+        CG_HIP(hipHostMalloc(&slot->host, capacity, hipHostMallocDefault));
+        slot->capacity = capacity;
+    }
+    CG_TRY(dev.reserve(bytes)); // (growth frees the old block, which waits for the kernel that may still read it)
+    memcpy(slot->host, records, bytes);
+    CG_HIP(hipMemcpyAsync(dev.ptr, slot->host, bytes, hipMemcpyHostToDevice, stream));
+    CG_HIP(hipEventRecord(slot->copied, stream));
+    slot->in_use = true;
+    *device_records = dev.ptr;
+    return Status{};
+}
+
 // Development switch: COMPEG_PIPELINE=split selects the two-kernel pipeline
 // (huffman_kernel -> HBM coefficients -> idct_composite_kernel); the default
 // is the fused single kernel.
@@ -2262,6 +2313,53 @@ Status compeg_decoder::pack_tensor(const compeg_tensor_spec &spec, void *dst, hi
     // (enqueue on another stream waits for this event: now it stands behind the pack as well)
     CG_HIP(hipEventRecord(decode_done, stream));
     decode_pending = true;
+    last_stream = stream;
+    return Status{};
+}
+
+// Resized tensor output: the ordering of pack_tensor; the per-image records travel on the pack's own stream in front of
+// the kernel (RecordStage).
+Status compeg_decoder::pack_tensor_resized(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_rect &crop,
+                                           void *dst, hipStream_t stream)
+{
+    CG_HIP(hipSetDevice(gpu->device));
+    alignas(8) uint8_t record[kResizeRecordBytes];
+    if (!make_resize_record(record, out.ptr, uint32_t(out_pitch), crop, spec.downscale, resize.out_width, resize.out_height))
+        return Status::error(COMPEG_E_INVALID_ARG, "tensor: the crop is smaller than the downscale factor");
+    if (!decode_done)
+        CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
+    if (decode_pending && stream != last_stream)
+        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
+    const void *records = nullptr;
+    CG_TRY(resize_records.upload(record, sizeof record, stream, &records));
+    CG_HIP(launch_resize_tensor(records, 1, spec, resize, dst, stream));
+    CG_HIP(hipEventRecord(decode_done, stream));
+    decode_pending = true;
+    last_stream = stream;
+    return Status{};
+}
+
+Status compeg_batch::pack_tensor_resized(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_rect *crops,
+                                         void *dst, hipStream_t stream)
+{
+    CG_HIP(hipSetDevice(gpu->device));
+    std::vector<uint8_t> records(count * kResizeRecordBytes);
+    for (size_t i = 0; i < count; i++) {
+        const compeg_rect whole{0, 0, descs[i].out_w, descs[i].out_h};
+        if (!make_resize_record(records.data() + i * kResizeRecordBytes, descs[i].out, descs[i].out_pitch, crops ? crops[i] : whole, spec.downscale, resize.out_width,
+                               resize.out_height))
+            return Status::error(COMPEG_E_INVALID_ARG, "tensor: a crop is smaller than the downscale factor");
+    }
+    if (decode_recorded && stream != last_stream) {
+        if (!decode_done)
+            CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
+        CG_HIP(hipEventRecord(decode_done, last_stream));
+        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
+    }
+    const void *device_records = nullptr;
+    CG_TRY(resize_records.upload(records.data(), records.size(), stream, &device_records));
+    CG_HIP(launch_resize_tensor(device_records, uint32_t(count), spec, resize, dst, stream));
+    // (no timing events; the next decode on another stream records decode_done on last_stream, behind this)
     last_stream = stream;
     return Status{};
 }

@@ -50,6 +50,28 @@ struct PinnedBuffer {
     Status reserve(size_t bytes);
 };
 
+// Small per-call records that a kernel reads from device memory (resized tensor output: one ResizeImage per image).
+// upload() copies them into pinned memory of its own and records the transfer on the caller's stream, so the records
+// reach the device in stream order and the call returns without waiting.  A pinned slot is written again only once
+// the copy out of it has run (its event says so); a call that finds every slot busy takes a new one.  The one device
+// block is written again only behind the kernel that read it: an object's packs run one behind the other on the
+// device (runtime.cpp: pack_tensor).
+struct RecordStage {
+    struct Slot {
+        void *host = nullptr;
+        size_t capacity = 0;
+        hipEvent_t copied = nullptr; // recorded behind the copy out of `host`
+        bool in_use = false;
+    };
+    std::vector<Slot> slots;
+    DeviceBuffer dev;
+    RecordStage() = default;
+    RecordStage(const RecordStage &) = delete;
+    RecordStage &operator=(const RecordStage &) = delete;
+    ~RecordStage(); // (the owner has waited for its streams)
+    Status upload(const void *records, size_t bytes, hipStream_t stream, const void **device_records);
+};
+
 // Fills the kernel-facing descriptor from the reference-format metadata.
 // Pointers are left for the caller to set.
 void fill_desc(const ImageData &img, ImageDesc &d);
@@ -129,6 +151,10 @@ struct compeg_decoder {
     // Tensor output (compeg_hip.h): the last image's corner of `out`, packed on `stream` behind the last decode; the next
     // decode waits for it.  spec and dst: checked by the caller.
     compeg::Status pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream);
+    // Resized tensor output: the same ordering; crop lies inside the last image (checked by the caller, like the specs)
+    compeg::RecordStage resize_records;
+    compeg::Status pack_tensor_resized(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_rect &crop,
+                                       void *dst, hipStream_t stream);
     compeg::Status check_scan_result(bool &fell_back);
     compeg::Status preprocess_on_device(const compeg::ImageData &img, hipStream_t stream, uint32_t &nwords,
                                         uint32_t &nstarts, uint32_t &span, bool &fell_back, size_t blob_bytes,
@@ -225,4 +251,8 @@ struct compeg_batch {
     bool output_decoded = false; // `out` holds a decode of the images uploaded last
     // Tensor output (compeg_hip.h): every image's output (all of one size: checked by the caller, like spec and dst)
     compeg::Status pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream);
+    // Resized tensor output: images of any sizes; crops: one per image, each inside its image (checked by the caller)
+    compeg::RecordStage resize_records;
+    compeg::Status pack_tensor_resized(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_rect *crops,
+                                       void *dst, hipStream_t stream);
 };

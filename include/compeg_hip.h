@@ -362,6 +362,52 @@ int compeg_decoder_pack_tensor(compeg_decoder *dec, const compeg_tensor_spec *sp
 int compeg_batch_pack_tensor(compeg_batch *batch, const compeg_tensor_spec *spec, void *device_dst,
                              size_t dst_bytes, void *hip_stream);
 
+/* ---- Resized tensor output (extension) --------------------------------------
+ * compeg_*_pack_tensor above gives W/k x H/k, and a batch only if its images are all of one size.  These calls give
+ * every image the same output extent whatever its size: a crop (optional) of the last decode is block-averaged as above,
+ * resized with one of two filters and converted, in one hand-written kernel.  Nothing else changes.
+ *
+ * k = downscale, the crop (cx, cy, cw, ch) (NULL: the whole image), ow x oh the output extent:
+ *   prefilter: pw = cw / k, ph = ch / k (rounded down; both at least 1);
+ *     P[c][j][i] = float(s) * (1 / k^2), s the integer sum of the channel over the k x k pixels at rows cy + k*j ..,
+ *     columns cx + k*i ..                                                        (exact in f32)
+ *   ratios: rx = float(double(pw) / double(ow)), ry = float(double(ph) / double(oh))
+ *   per axis (x shown): a = float(x) + 0.5f;  b = a * rx
+ *     COMPEG_RESIZE_NEAREST:  i = min(int(floor(b)), pw - 1)
+ *     COMPEG_RESIZE_BILINEAR: s = max(b - 0.5f, 0);  i0 = min(int(floor(s)), pw - 1);  i1 = min(i0 + 1, pw - 1);
+ *                             w1 = s - float(i0);  w0 = 1.0f - w1      (half-pixel centres, no antialiasing)
+ *   value: nearest m = P[c][j][i]; bilinear top = (P[j0][i0] * wx0) + (P[j0][i1] * wx1), bot likewise on row j1,
+ *     m = (top * wy0) + (bot * wy1)
+ *   v = (m * scale[c]) + bias[c], converted and stored as above.
+ * Every operation is one rounded f32 operation, never fused.  With ow = pw and oh = ph both filters give
+ * compeg_*_pack_tensor of the crop, element for element.  No pixel outside the crop is read.
+ * Destination: [3][oh][ow] for a decoder, [count][3][oh][ow] for a batch, tight, aligned to its element size.  A
+ * batch's images may differ in size; every image gets the same output extent. */
+#define COMPEG_RESIZE_NEAREST 0
+#define COMPEG_RESIZE_BILINEAR 1
+typedef struct compeg_resize_spec {
+    uint32_t out_width, out_height, filter, reserved; /* 1..65535 each way; COMPEG_RESIZE_*; reserved = 0 */
+} compeg_resize_spec;
+typedef struct compeg_rect {
+    uint32_t x, y, width, height;
+} compeg_rect;
+/* No device needed: validates, and reports the prefiltered crop's extent (each output optional) and the byte count of
+ * one image's tensor (3 * oh * ow * element size) for a WxH source.  COMPEG_E_INVALID_ARG for what compeg_tensor_shape
+ * rejects and for: an output extent of 0 or above 65535, an unknown filter, reserved != 0, a crop with a side of 0 or
+ * one that leaves the image, a crop (or image) smaller than downscale either way. */
+int compeg_resized_tensor_shape(const compeg_tensor_spec *spec, const compeg_resize_spec *resize, uint32_t width,
+                                uint32_t height, const compeg_rect *crop, uint32_t *pre_width, uint32_t *pre_height,
+                                size_t *bytes_per_image);
+/* Like compeg_*_pack_tensor in everything they say about hip_stream, ordering, timing events and the decoder's texture.
+ * crop / crops: NULL for whole images; one rectangle for a decoder, one per image for a batch (copied before the call
+ * returns). */
+int compeg_decoder_pack_tensor_resized(compeg_decoder *dec, const compeg_tensor_spec *spec,
+                                       const compeg_resize_spec *resize, const compeg_rect *crop, void *device_dst,
+                                       size_t dst_bytes, void *hip_stream);
+int compeg_batch_pack_tensor_resized(compeg_batch *batch, const compeg_tensor_spec *spec,
+                                     const compeg_resize_spec *resize, const compeg_rect *crops, void *device_dst,
+                                     size_t dst_bytes, void *hip_stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -29,6 +29,26 @@ pub struct compeg_tensor_spec {
     pub bias: [c_float; 3],
 }
 
+/// The output extent and the filter of `compeg_*_pack_tensor_resized` (compeg_hip.h, "Resized tensor output").
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct compeg_resize_spec {
+    pub out_width: u32,
+    pub out_height: u32,
+    pub filter: u32,
+    pub reserved: u32,
+}
+
+/// A crop in pixels.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct compeg_rect {
+    pub x: u32,
+    pub y: u32,
+    pub width: u32,
+    pub height: u32,
+}
+
 pub const COMPEG_OK: c_int = 0;
 pub const COMPEG_E_INVALID_ARG: c_int = -1;
 pub const COMPEG_E_UNSUPPORTED: c_int = -2;
@@ -52,6 +72,8 @@ pub const COMPEG_TENSOR_BF16: u32 = 2;
 pub const COMPEG_TENSOR_F32: u32 = 3;
 pub const COMPEG_TENSOR_RGB: u32 = 0;
 pub const COMPEG_TENSOR_BGR: u32 = 1;
+pub const COMPEG_RESIZE_NEAREST: u32 = 0;
+pub const COMPEG_RESIZE_BILINEAR: u32 = 1;
 
 extern "C" {
     pub fn compeg_last_error() -> *const c_char;
@@ -152,4 +174,15 @@ extern "C" {
                                       dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
     pub fn compeg_batch_pack_tensor(batch: *mut compeg_batch, spec: *const compeg_tensor_spec, device_dst: *mut c_void,
                                     dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+
+    // Resized tensor output (extension)
+    pub fn compeg_resized_tensor_shape(spec: *const compeg_tensor_spec, resize: *const compeg_resize_spec, width: u32, height: u32,
+                                       crop: *const compeg_rect, pre_width: *mut u32, pre_height: *mut u32,
+                                       bytes_per_image: *mut usize) -> c_int;
+    pub fn compeg_decoder_pack_tensor_resized(dec: *mut compeg_decoder, spec: *const compeg_tensor_spec,
+                                              resize: *const compeg_resize_spec, crop: *const compeg_rect, device_dst: *mut c_void,
+                                              dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_batch_pack_tensor_resized(batch: *mut compeg_batch, spec: *const compeg_tensor_spec,
+                                            resize: *const compeg_resize_spec, crops: *const compeg_rect, device_dst: *mut c_void,
+                                            dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
 }

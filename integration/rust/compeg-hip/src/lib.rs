@@ -120,6 +120,45 @@ impl TensorSpec {
     }
 }
 
+/// Filter of a resized pack (`COMPEG_RESIZE_*`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum ResizeFilter {
+    Nearest = 0,
+    Bilinear = 1,
+}
+
+/// A crop in pixels (`compeg_rect`).
+pub type Rect = ffi::compeg_rect;
+
+/// The fixed output extent of `Decoder::pack_tensor_resized` / `Batch::pack_tensor_resized` (extension; compeg_hip.h,
+/// "Resized tensor output"): the crop is block-averaged as `TensorSpec::downscale` says, then resized to `width` x
+/// `height` -- bilinear with half-pixel centres and no antialiasing, or nearest.
+#[derive(Clone, Copy, Debug)]
+pub struct ResizeSpec {
+    pub width: u32,
+    pub height: u32,
+    pub filter: ResizeFilter,
+}
+
+impl ResizeSpec {
+    pub fn new(width: u32, height: u32) -> Self {
+        ResizeSpec { width, height, filter: ResizeFilter::Bilinear }
+    }
+
+    fn raw(&self) -> ffi::compeg_resize_spec {
+        ffi::compeg_resize_spec { out_width: self.width, out_height: self.height, filter: self.filter as u32, reserved: 0 }
+    }
+
+    /// `(pre_width, pre_height, bytes)`: the extent of the block-averaged crop of a `width` x `height` image that the
+    /// filter reads, and one image's tensor in bytes; no device needed.
+    pub fn shape(&self, tensor: &TensorSpec, width: u32, height: u32, crop: Option<&Rect>) -> Result<(u32, u32, usize)> {
+        let (mut w, mut h, mut n) = (0, 0, 0);
+        let crop = crop.map_or(ptr::null(), |c| c as *const Rect);
+        check(unsafe { ffi::compeg_resized_tensor_shape(&tensor.raw(), &self.raw(), width, height, crop, &mut w, &mut h, &mut n) })?;
+        Ok((w, h, n))
+    }
+}
+
 /// Device + stream + loaded gfx950 code object.  Immutable after creation and
 /// reference-counted inside the library; share it as `Arc<Gpu>` like the reference.
 pub struct Gpu {
@@ -362,6 +401,17 @@ impl Decoder {
         check(ffi::compeg_decoder_pack_tensor(self.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
     }
 
+    /// Extension: like `pack_tensor`, with `crop` of the last decoded image (`None`: all of it) resized to the extent of
+    /// `resize`, giving `[3, resize.height, resize.width]` at `device_dst`.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn pack_tensor_resized(&mut self, spec: &TensorSpec, resize: &ResizeSpec, crop: Option<&Rect>, device_dst: *mut c_void,
+                                      dst_bytes: usize, stream: Stream) -> Result<()> {
+        let crop = crop.map_or(ptr::null(), |c| c as *const Rect);
+        check(ffi::compeg_decoder_pack_tensor_resized(self.raw.as_ptr(), &spec.raw(), &resize.raw(), crop, device_dst, dst_bytes, stream.0))
+    }
+
     /// Test helper (the reference's tests copy the texture to a buffer): waits and
     /// returns the image's `width x height` corner, tightly packed.
     pub fn read_output(&mut self, width: u32, height: u32) -> Result<Vec<u8>> {
@@ -517,6 +567,24 @@ impl Batch {
     /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
     pub unsafe fn pack_tensor(&mut self, spec: &TensorSpec, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
         check(ffi::compeg_batch_pack_tensor(self.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
+    }
+
+    /// Records on `stream` the resized pack of the last decode's images, of whatever sizes, into
+    /// `[len, 3, resize.height, resize.width]` at `device_dst`; `crops`: `None` for whole images, or one per image.
+    /// `wait` covers it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn pack_tensor_resized(&mut self, spec: &TensorSpec, resize: &ResizeSpec, crops: Option<&[Rect]>, device_dst: *mut c_void,
+                                      dst_bytes: usize, stream: Stream) -> Result<()> {
+        if let Some(c) = crops {
+            if c.len() != self.len() {
+                let message = format!("pack_tensor_resized: {} crops for a batch of {} images", c.len(), self.len());
+                return Err(Error { message, code: ffi::COMPEG_E_INVALID_ARG });
+            }
+        }
+        let crops = crops.map_or(ptr::null(), |c| c.as_ptr());
+        check(ffi::compeg_batch_pack_tensor_resized(self.raw.as_ptr(), &spec.raw(), &resize.raw(), crops, device_dst, dst_bytes, stream.0))
     }
 
     pub fn wait(&mut self) -> Result<()> {

@@ -1,0 +1,149 @@
+"""Resized tensor output (Batch.pack_tensor_resized) against what a user writes today.
+
+Resident batches of 4:2:2 DRI=4 frames, decoded once.  Per configuration: the resized pack alone, timed with HIP
+events on its stream, launch by launch in turn with the chain a caller of pack_tensor writes --
+
+    Batch.pack_tensor(f32, k)  ->  F.interpolate(mode="bilinear", antialias=False)  ->  * scale + bias  ->  .to(dtype)
+
+(f32 so that nothing is rounded twice; u8: rounded and clamped before the cast) -- whose last bits may differ (it is
+a timing baseline only).  The mixed batch has four sizes: its baseline is one such chain per size group, each group a
+resident batch of its own, written into its slice of the output.  Every configuration is warmed up first and the
+clock primed as bench.py does it.  Needs the card: there is no CPU path.  Writes a table (default
+profiles/tensor_resize.txt) and prints it.
+
+    python tools/resize_probe.py [--batch 256] [--distinct 16] [--reps 10] [--out profiles/tensor_resize.txt]
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+PRIME_SECONDS = 0.08
+MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+# (name, ((width, height), ...) -- the batch's slots split evenly between them --, output size, element type, k)
+CONFIGS = (("4K -> 224x224 f16 k=8", ((3840, 2160),), (224, 224), "f16", 8),
+           ("4K -> 224x224 f16 k=1", ((3840, 2160),), (224, 224), "f16", 1),
+           ("1080p -> 640x640 f16 k=1", ((1920, 1080),), (640, 640), "f16", 1),
+           ("960x720 -> 224x224 u8 k=2", ((960, 720),), (224, 224), "u8", 2),
+           ("mixed -> 224x224 f16 k=1", ((1920, 1080), (1280, 720), (960, 720), (640, 360)), (224, 224), "f16", 1))
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--batch", type=int, default=256)
+    p.add_argument("--distinct", type=int, default=16, help="distinct synthetic frames per size (timings do not depend on the content)")
+    p.add_argument("--reps", type=int, default=10, help="timed launches per configuration, of the pack and of the chain in turn")
+    p.add_argument("--threads", type=int, default=16)
+    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "tensor_resize.txt"))
+    args = p.parse_args()
+
+    import torch
+    import torch.nn.functional as F
+
+    import compeg_amd
+    from tools import synth
+
+    if not torch.cuda.is_available():
+        raise SystemExit("resize_probe: no GPU (nothing here is measured without one)")
+    n = args.batch
+    gpu = compeg_amd.Gpu.open(0)
+    stream = torch.cuda.Stream()
+    handle = stream.cuda_stream
+    torch_type = {"u8": torch.uint8, "f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}
+    made = {}
+
+    def images_of(w, h):
+        if (w, h) not in made:
+            count = min(args.distinct, n)
+            with ThreadPoolExecutor(args.threads) as ex:
+                jpegs = list(ex.map(lambda i: synth.make_jpeg(w, h, seed=0xC0FFEE + i, quality=85, ri=4), range(count)))
+            made[(w, h)] = [compeg_amd.ImageData(j, copy=False) for j in jpegs], jpegs
+        return made[(w, h)][0]
+
+    def resident(items):
+        batch = compeg_amd.Batch(gpu)
+        batch.upload(items, host_threads=args.threads)
+        batch.decode(handle)
+        batch.wait()
+        return batch
+
+    lines = [f"resized tensor output: {n} resident 4:2:2 DRI=4 frames per configuration, decoded once; {gpu.name()}",
+             f"resized = Batch.pack_tensor_resized alone, HIP events on its stream; chain = pack_tensor(f32, k) -> F.interpolate(bilinear) -> "
+             f"* scale + bias -> .to(dtype), per size group, launch by launch in turn; median of {args.reps} (min .. max)",
+             f"{'configuration':<28} {'resized ms':>24} {'chain ms':>26} {'chain/resized':>13}"]
+    slower = []
+    for name, sizes, (ow, oh), dtype, k in CONFIGS:
+        per = n // len(sizes)
+        groups = [[images_of(w, h)[i % len(images_of(w, h))] for i in range(per)] for w, h in sizes]
+        total = per * len(sizes)
+        mixed = resident([im for g in groups for im in g])
+        singles = [mixed] if len(sizes) == 1 else [resident(g) for g in groups]
+        scale = [1.0] * 3 if dtype == "u8" else [1.0 / (255.0 * s) for s in STD]
+        bias = [0.0] * 3 if dtype == "u8" else [-m / s for m, s in zip(MEAN, STD)]
+        dst = torch.empty((total, 3, oh, ow), dtype=torch_type[dtype], device="cuda")
+        ref = torch.empty((total, 3, oh, ow), dtype=torch_type[dtype], device="cuda")
+        with torch.cuda.stream(stream):
+            ts = torch.tensor(scale, dtype=torch.float32, device="cuda").view(1, 3, 1, 1)
+            tb = torch.tensor(bias, dtype=torch.float32, device="cuda").view(1, 3, 1, 1)
+            full = [torch.empty((per, 3, h // k, w // k), dtype=torch.float32, device="cuda") for w, h in sizes]
+
+        def prime():
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < PRIME_SECONDS:
+                mixed.decode(handle)
+                mixed.wait()
+
+        def resized():
+            mixed.pack_tensor_resized(dst, (ow, oh), dtype=dtype, downscale=k, scale=scale, bias=bias, hip_stream=handle)
+
+        def chain():
+            for g, (batch, tmp) in enumerate(zip(singles, full)):
+                batch.pack_tensor(tmp, dtype="f32", downscale=k, hip_stream=handle)
+                x = F.interpolate(tmp, size=(oh, ow), mode="bilinear", align_corners=False, antialias=False)
+                x = x * ts + tb
+                if dtype == "u8":
+                    x = x.round().clamp(0, 255)
+                ref[g * per:(g + 1) * per] = x.to(torch_type[dtype])
+
+        with torch.cuda.stream(stream):
+            for _ in range(2):   # warm-up of both: code objects, the allocator's blocks
+                resized()
+                chain()
+            stream.synchronize()
+            prime()
+            ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.reps)]
+            for e0, e1, e2 in ev:
+                e0.record(stream)
+                resized()
+                e1.record(stream)
+                chain()
+                e2.record(stream)
+            stream.synchronize()
+        t_new = [a.elapsed_time(b) for a, b, _ in ev]
+        t_chain = [b.elapsed_time(c) for _, b, c in ev]
+        mn, mc = statistics.median(t_new), statistics.median(t_chain)
+        worst = float((dst.float() - ref.float()).abs().max())
+        lines.append(f"{name:<28} {mn:8.3f} ({min(t_new):.3f} .. {max(t_new):.3f}) {mc:9.3f} ({min(t_chain):.3f} .. {max(t_chain):.3f}) "
+                     f"{mc / mn:13.2f}   max |resized - chain| {worst:.4g}")
+        spread = max(max(t_new) - min(t_new), max(t_chain) - min(t_chain))
+        if mn - mc > spread:
+            slower.append(name)
+        del dst, ref, full, mixed, singles
+        torch.cuda.empty_cache()
+
+    lines.append("resized slower than the chain beside it by more than the rows' own min-to-max spread: " + ("; ".join(slower) if slower else "none"))
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+    print(text, end="")
+
+
+if __name__ == "__main__":
+    main()
