@@ -18,7 +18,7 @@ FIVE = ((16, 8), (17, 9), (50, 26), (66, 26), (330, 70))
 SENTINEL = 0x5C
 ADMISSIBLE = {(w, h): [k for k in (1, 2, 4, 8) if w >= k and h >= k] for w, h in SIZES}
 
-torch = ca = rr = gpu = stream = None   # set by main(): torch first
+torch = ca = rr = ne = gpu = stream = None   # set by main(): torch first
 
 
 class Raises:
@@ -272,6 +272,56 @@ def rejections():
     stream.synchronize()
 
 
+_decoded = {}
+
+
+def _edge_decoder(frame):
+    """The decoder that holds numeric_edges' frame, decoded once for all the sets."""
+    if frame not in _decoded:
+        jpeg, rgba = ne.FRAMES[frame]()
+        dec = ca.Decoder(gpu)
+        dec.decode_blocking(ca.ImageData(jpeg))
+        _decoded[frame] = (dec, rgba)
+    return _decoded[frame]
+
+
+def _edge_pack(name, dtype, frame, k, size, filter, order, crop=None):
+    """One resized pack of a set of tests/numeric_edges.py, every element against the formula; the device tensor."""
+    _, scale, bias = ne.SETS[name]
+    dec, rgba = _edge_decoder(frame)
+    dst = torch.empty((3, size[1], size[0]), dtype=_torch_type(dtype), device="cuda")
+    dec.pack_tensor_resized(dst, size, crop=crop, filter=filter, dtype=dtype, downscale=k, scale=scale, bias=bias, order=order,
+                            hip_stream=stream.cuda_stream)
+    stream.synchronize()
+    _check(_host(dst, dtype), ne.expected_resized(rgba, size, k, name, dtype, order, filter, crop), dtype,
+           f"{name} {frame} k={k} crop {crop} -> {size} {dtype} {filter} {order}")
+    return dst
+
+
+def numeric_edges(name):
+    """One (scale, bias) set of tests/numeric_edges.py on the device's own conversions and arithmetic: nearest at the
+    ramp's identity extent (which is pack_tensor of the set, infinities included), bilinear with taps that straddle the
+    ramp's tiles; the ImageNet pair as float32, where a contracted tap or lerp shows."""
+    dtypes, scale, bias = ne.SETS[name]
+    for n, dtype in enumerate(dtypes):
+        order = ("rgb", "bgr")[n % 2]
+        dec, _ = _edge_decoder("ramp")
+        a = torch.empty((3, ne.RAMP_H, ne.RAMP_W), dtype=_torch_type(dtype), device="cuda")
+        dec.pack_tensor(a, dtype=dtype, downscale=1, scale=scale, bias=bias, order=order, hip_stream=stream.cuda_stream)
+        b = _edge_pack(name, dtype, "ramp", 1, (ne.RAMP_W, ne.RAMP_H), "nearest", order)
+        assert torch.equal(a, b), f"{name} {dtype}: nearest at the identity extent differs from pack_tensor"   # (no NaN: equal means equal)
+        frame, k, size, crop = ne.RESIZE_EDGE
+        _edge_pack(name, dtype, frame, k, size, "bilinear", ("bgr", "rgb")[n % 2], crop)
+    if name == "imagenet_f32":
+        for n, (frame, k, size, crop) in enumerate(ne.RESIZE_CONTRACTION):
+            _edge_pack(name, "f32", frame, k, size, "bilinear", ("rgb", "bgr")[n % 2], crop)
+
+
+# (tests/numeric_edges.py's sets by name: importing it here would bring the oracle and the encoder in front of torch)
+EDGE_SETS = ("f16_ties", "f16_overflow", "f16_subnormal", "f16_inf", "bf16_ties", "bf16_overflow", "f32_denormal", "f32_inf", "u8_ties",
+             "u8_clamp", "u8_clamp2", "imagenet_f32")
+
+
 def _cases():
     cases = {}
     for w, h in SIZES:
@@ -287,6 +337,8 @@ def _cases():
     cases["decoder_ordering_without_host_waits"] = (decoder_ordering_without_host_waits, ())
     cases["batch_ordering_across_streams"] = (batch_ordering_across_streams, ())
     cases["rejections"] = (rejections, ())
+    for name in EDGE_SETS:
+        cases[f"numeric_edges[{name}]"] = (numeric_edges, (name,))
     return cases
 
 
@@ -294,7 +346,7 @@ CASES = _cases()
 
 
 def main(out_path):
-    global torch, ca, rr, gpu, stream
+    global torch, ca, rr, ne, gpu, stream
     import torch   # first: see the module's docstring
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for p in (root, os.path.join(root, "tests")):
@@ -302,6 +354,8 @@ def main(out_path):
             sys.path.insert(0, p)
     import compeg_amd as ca
     import resize_reference as rr
+    import numeric_edges as ne
+    assert tuple(ne.SETS) == EDGE_SETS and ne.denormals_kept()
     gpu = ca.Gpu.open(0)
     stream = torch.cuda.Stream()
     results = {}

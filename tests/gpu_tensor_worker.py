@@ -18,7 +18,7 @@ SIZES = ((16, 8), (17, 9), (50, 26), (330, 70))
 SENTINEL = 0x5C
 ADMISSIBLE = {(w, h): [k for k in (1, 2, 4, 8) if w >= k and h >= k] for w, h in SIZES}
 
-torch = ca = tr = gpu = stream = None   # set by main(): torch first
+torch = ca = tr = ne = gpu = stream = None   # set by main(): torch first
 
 
 class Raises:
@@ -213,6 +213,64 @@ def batch_ordering_across_streams():
     assert np.array_equal(batch.read_output(1), frames[1][1])
 
 
+_decoded = {}
+
+
+def _edge_decoder(frame):
+    """The decoder that holds numeric_edges' frame, decoded once for all the sets."""
+    if frame not in _decoded:
+        jpeg, rgba = ne.FRAMES[frame]()
+        dec = ca.Decoder(gpu)
+        dec.decode_blocking(ca.ImageData(jpeg))
+        _decoded[frame] = (dec, rgba)
+    return _decoded[frame]
+
+
+def numeric_edges(name):
+    """One (scale, bias) set of tests/numeric_edges.py: the ramp at k = 1, the noisy frame at k = 2 and 8, every element
+    against the formula -- ties, subnormals, overflow, infinities, the clamp, denormal float32 on the device's own
+    conversions."""
+    dtypes, scale, bias = ne.SETS[name]
+    n = 0
+    for dtype in dtypes:
+        for frame, k in ne.PACKS:
+            dec, rgba = _edge_decoder(frame)
+            h, w = rgba.shape[:2]
+            order = ("rgb", "bgr")[n % 2]
+            n += 1
+            dst = torch.empty((3, h // k, w // k), dtype=_torch_type(dtype), device="cuda")
+            dec.pack_tensor(dst, dtype=dtype, downscale=k, scale=scale, bias=bias, order=order, hip_stream=stream.cuda_stream)
+            stream.synchronize()
+            _check(_host(dst, dtype), ne.expected(rgba, k, name, dtype, order), dtype, f"{name} {frame} k={k} {dtype} {order}")
+
+
+def numeric_edges_batch():
+    """The ramp and its mirror image as a batch, f16 subnormals and the u8 clamp, one element into a sentinel buffer."""
+    frames = [ne.ramp(), ne.ramp_flipped()]
+    batch = ca.Batch(gpu)
+    batch.upload([ca.ImageData(j) for j, _ in frames])
+    batch.decode()
+    for name in ("f16_subnormal", "u8_clamp"):
+        (dtype,), scale, bias = ne.SETS[name]
+        shape, per_image = ca.tensor_shape(ne.RAMP_W, ne.RAMP_H, dtype=dtype, downscale=1)
+        needed, esize = 2 * per_image, tr.ELEM_BYTES[dtype]
+        buf = torch.full((64 + esize + needed + 64,), SENTINEL, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        batch.pack_tensor((buf.data_ptr() + 64 + esize, needed), dtype=dtype, downscale=1, scale=scale, bias=bias, hip_stream=stream.cuda_stream)
+        batch.wait()   # (covers the pack)
+        raw = buf.cpu().numpy().tobytes()
+        lo, hi = 64 + esize, 64 + esize + needed
+        assert raw[:lo] == bytes([SENTINEL]) * lo and raw[hi:] == bytes([SENTINEL]) * 64, f"{name}: sentinels overwritten"
+        got = tr.from_bytes(raw[lo:hi], dtype, (2,) + shape)
+        for i, (_, rgba) in enumerate(frames):
+            _check(got[i], ne.expected(rgba, 1, name, dtype), dtype, f"{name} slot {i}")
+
+
+# (tests/numeric_edges.py's sets by name: importing it here would bring the oracle and the encoder in front of torch)
+EDGE_SETS = ("f16_ties", "f16_overflow", "f16_subnormal", "f16_inf", "bf16_ties", "bf16_overflow", "f32_denormal", "f32_inf", "u8_ties",
+             "u8_clamp", "u8_clamp2", "imagenet_f32")
+
+
 def _cases():
     cases = {}
     for w, h in SIZES:
@@ -228,6 +286,9 @@ def _cases():
     cases["wide_row"] = (wide_row, ())
     cases["decoder_ordering_without_host_waits"] = (decoder_ordering_without_host_waits, ())
     cases["batch_ordering_across_streams"] = (batch_ordering_across_streams, ())
+    for name in EDGE_SETS:
+        cases[f"numeric_edges[{name}]"] = (numeric_edges, (name,))
+    cases["numeric_edges_batch"] = (numeric_edges_batch, ())
     return cases
 
 
@@ -235,7 +296,7 @@ CASES = _cases()
 
 
 def main(out_path):
-    global torch, ca, tr, gpu, stream
+    global torch, ca, tr, ne, gpu, stream
     import torch   # first: see the module's docstring
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for p in (root, os.path.join(root, "tests")):
@@ -243,6 +304,8 @@ def main(out_path):
             sys.path.insert(0, p)
     import compeg_amd as ca
     import tensor_reference as tr
+    import numeric_edges as ne
+    assert tuple(ne.SETS) == EDGE_SETS and ne.denormals_kept()
     gpu = ca.Gpu.open(0)
     stream = torch.cuda.Stream()
     results = {}

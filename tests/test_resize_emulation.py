@@ -11,6 +11,9 @@ import subprocess
 
 import pytest
 
+import numpy as np
+
+import numeric_edges as ne
 import resize_reference as rr
 from conftest import ROOT
 
@@ -20,11 +23,15 @@ SENTINEL = 0x5C
 PAD = 0xA5
 
 
-def _case(images, size, k, dtype, filter, order, offset=None, identity=False):
-    """images: ((w, h, seed, crop or None), ...)"""
-    scale, bias = rr.params(dtype, identity)
-    return dict(images=tuple(images), size=size, k=k, dtype=dtype, filter=filter, order=order, scale=scale, bias=bias,
-                offset=64 + rr.ELEM_BYTES[dtype] if offset is None else offset)
+def _case(images, size, k, dtype, filter, order, offset=None, identity=False, edge=None):
+    """images: ((w, h, seed, crop or None), ...); a seed that is a name is a frame of tests/numeric_edges.py, and edge
+    the set of its whose scale and bias the case takes"""
+    scale, bias = rr.params(dtype, identity) if edge is None else ne.SETS[edge][1:]
+    c = dict(images=tuple(images), size=size, k=k, dtype=dtype, filter=filter, order=order, scale=scale, bias=bias,
+             offset=64 + rr.ELEM_BYTES[dtype] if offset is None else offset)
+    if edge is not None:
+        c["edge"] = edge
+    return c
 
 
 def _cases():
@@ -67,6 +74,17 @@ def _cases():
     for w, h, k, size in ((16, 8, 1, (64, 64)), (330, 70, 1, (64, 64)), (330, 70, 2, (33, 7)), (50, 26, 1, (48, 16))):
         for dtype in rr.DTYPES:
             cases.append(_case(((w, h, 3, None), (w, h, 4, None)), size, k, dtype, "bilinear", "bgr", offset=64))
+    # the numeric edges (tests/numeric_edges.py): every set on the ramp at k = 1 (taps that straddle its tiles) and on
+    # the noisy frame at k = 2 and k = 8, aligned and misaligned by one element; nearest at the ramp's identity extent
+    frame, k1, size1, crop1 = ne.RESIZE_EDGE
+    for name, dtype in ne.SET_DTYPES:
+        for offset in (64, None):
+            n += 1
+            order = ("rgb", "bgr")[n % 2]
+            cases.append(_case(((ne.RAMP_W, ne.RAMP_H, frame, crop1),), size1, k1, dtype, "bilinear", order, offset=offset, edge=name))
+            cases.append(_case(((*ne.NOISY, "noisy", None),), (64, 64), 2, dtype, "bilinear", order, offset=offset, edge=name))
+            cases.append(_case(((*ne.NOISY, "noisy", None),), (33, 7), 8, dtype, "bilinear", order, offset=offset, edge=name))
+        cases.append(_case(((ne.RAMP_W, ne.RAMP_H, "ramp", None),), (ne.RAMP_W, ne.RAMP_H), 1, dtype, "nearest", "rgb", edge=name))
     return cases
 
 
@@ -74,16 +92,27 @@ CASES = _cases()
 
 
 def _id(c):
-    images = "+".join(f"{w}x{h}" + ("" if crop is None else "c%d.%d.%d.%d" % crop) for w, h, _, crop in c["images"])
+    images = "+".join((seed if isinstance(seed, str) else "") + f"{w}x{h}" + ("" if crop is None else "c%d.%d.%d.%d" % crop)
+                      for w, h, seed, crop in c["images"])
+    if "edge" in c:
+        images = f"{c['edge']}-{images}"
     return f"{images}-to{c['size'][0]}x{c['size'][1]}-k{c['k']}-{c['dtype']}-{c['filter']}-{c['order']}-at{c['offset']}"
+
+
+def _rgba(w, h, seed):
+    """The frame of a case's image: tensor_reference's by seed, or one of tests/numeric_edges.py by name."""
+    if isinstance(seed, str):
+        rgba = ne.FRAMES[seed]()[1]
+        assert rgba.shape == (h, w, 4)
+        return rgba
+    return rr.frame(w, h, seed=seed)[1]
 
 
 def _allocation(w, h, seed):
     """(pitch, rows, bytes) of one image as the runtime allocates it."""
-    import numpy as np
     pitch, rows = (w + 15) // 16 * 64, (h + 15) // 16 * 16
     alloc = np.full((rows, pitch), PAD, dtype=np.uint8)
-    alloc[:h, :w * 4] = rr.frame(w, h, seed=seed)[1].reshape(h, w * 4)
+    alloc[:h, :w * 4] = _rgba(w, h, seed).reshape(h, w * 4)
     return pitch, rows, alloc.tobytes()
 
 
@@ -133,5 +162,6 @@ def test_lane_body_matches_the_formula_and_stays_inside_the_tensor(packed, index
     assert buf[hi:] == bytes([SENTINEL]) * (len(buf) - hi), "bytes behind the tensor were written"
     got = rr.from_bytes(buf[lo:hi], c["dtype"], (len(c["images"]), 3, oh, ow))
     for i, (w, h, seed, crop) in enumerate(c["images"]):
-        want = rr.expected(rr.frame(w, h, seed=seed)[1], c["size"], c["k"], c["dtype"], c["scale"], c["bias"], c["order"], c["filter"], crop)
+        with np.errstate(over="ignore"):   # (the edge sets overflow to infinity on purpose)
+            want = rr.expected(_rgba(w, h, seed), c["size"], c["k"], c["dtype"], c["scale"], c["bias"], c["order"], c["filter"], crop)
         assert rr.same(got[i], want, c["dtype"]), f"image {i}: {int((got[i] != want).sum())} of {want.size} elements differ"

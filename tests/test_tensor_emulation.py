@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import numeric_edges as ne
 import tensor_reference as tr
 from conftest import ROOT
 
@@ -37,6 +38,16 @@ def _cases():
     for w, h, k in ((16, 8, 1), (330, 70, 1), (330, 70, 2), (50, 26, 1)):
         for dtype in tr.DTYPES:
             cases.append(dict(w=w, h=h, k=k, dtype=dtype, order="bgr", scale=tr.IMAGENET_SCALE, bias=tr.IMAGENET_BIAS, images=2, offset=64))
+    # the numeric edges (tests/numeric_edges.py): every set on its frames, aligned and misaligned by one element --
+    # the software f16's subnormal, overflow and infinity branches, the u8 clamp on infinities, denormal float32
+    for name, dtype in ne.SET_DTYPES:
+        _, scale, bias = ne.SETS[name]
+        for frame, k in ne.PACKS:
+            for offset in (64, 64 + tr.ELEM_BYTES[dtype]):
+                n += 1
+                w, h = ne.EXTENT[frame]
+                cases.append(dict(w=w, h=h, k=k, dtype=dtype, order=("rgb", "bgr")[n % 2], scale=scale, bias=bias, images=1, offset=offset,
+                                  frames=(frame,), edge=name))
     return cases
 
 
@@ -44,14 +55,19 @@ CASES = _cases()
 
 
 def _id(c):
-    return f"{c['w']}x{c['h']}-k{c['k']}-{c['dtype']}-{c['order']}-n{c['images']}-at{c['offset']}"
+    edge = f"{c['edge']}-{c['frames'][0]}-" if "edge" in c else ""
+    return f"{edge}{c['w']}x{c['h']}-k{c['k']}-{c['dtype']}-{c['order']}-n{c['images']}-at{c['offset']}"
 
 
 def _source(c):
     """The images' allocations (pitch, rows, bytes) and their RGBA."""
     w, h = c["w"], c["h"]
     pitch, rows = (w + 15) // 16 * 64, (h + 15) // 16 * 16
-    frames = [tr.frame(w, h, seed=3 + i)[1] for i in range(c["images"])]
+    if "frames" in c:   # handed in by name (tests/numeric_edges.py)
+        frames = [ne.FRAMES[name]()[1] for name in c["frames"]]
+        assert len(frames) == c["images"] and all(f.shape == (h, w, 4) for f in frames)
+    else:
+        frames = [tr.frame(w, h, seed=3 + i)[1] for i in range(c["images"])]
     alloc = np.full((c["images"], rows, pitch), PAD, dtype=np.uint8)
     for i, f in enumerate(frames):
         alloc[i, :h, :w * 4] = f.reshape(h, w * 4)
@@ -100,7 +116,8 @@ def test_lane_body_matches_the_formula_and_stays_inside_the_tensor(packed, index
     got = tr.from_bytes(buf[lo:hi], c["dtype"], (c["images"], 3, oh, ow))
     frames = _source(c)[3]
     for i, f in enumerate(frames):
-        want = tr.expected(f, c["k"], c["dtype"], c["scale"], c["bias"], c["order"])
+        with np.errstate(over="ignore"):   # (the edge sets overflow to infinity on purpose)
+            want = tr.expected(f, c["k"], c["dtype"], c["scale"], c["bias"], c["order"])
         assert tr.same(got[i], want, c["dtype"]), f"image {i}: {int((got[i] != want).sum())} of {want.size} elements differ"
 
 
