@@ -21,7 +21,9 @@ struct ScanDesc {
     uint32_t expected = 0;   // restart intervals the frame header announces (span_kernel only)
     uint32_t *result;        // [8]: intervals counted, kept bytes, output words, flags (bit 0: FF run too long; bit 1:
                              // a marker other than RSTn inside the segment -- it ends earlier than the caller said),
-                             // widest 64-interval span in words (span_kernel), 3 unused
+                             // widest 64-interval span in words (span_kernel), 3 unused.  The flags are OR-ed into
+                             // result[3]: the caller clears it before the launch; every other word the kernels
+                             // write is stored whole, whatever the memory held (words_out's padding included)
     // optional: where to drop the output word count and the number of start positions kept
     // (the nwords / nstarts fields of the image descriptor a following decode kernel reads)
     uint32_t *patch_nwords = nullptr;
