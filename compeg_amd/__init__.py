@@ -65,14 +65,18 @@ def tensor_shape(width, height, dtype="f16", downscale=1):
 RESIZE_FILTERS = {"nearest": 0, "bilinear": 1}
 
 
-def _resize_spec(size, filter):
-    """compeg_resize_spec from size = (ow, oh) and a filter's name (or the header's number, which the library checks)."""
+RESIZE_ANTIALIAS = 0x100   # COMPEG_RESIZE_ANTIALIAS: a flag beside the filter, for "bilinear" only (the library checks)
+
+
+def _resize_spec(size, filter, antialias=False):
+    """compeg_resize_spec from size = (ow, oh), a filter's name (or the header's number, which the library checks) and the
+    antialias flag."""
     if isinstance(filter, str) and filter not in RESIZE_FILTERS:
         raise Error(f"unknown resize filter {filter!r} (one of {', '.join(RESIZE_FILTERS)})")
     ow, oh = size
     spec = ResizeSpec()
     spec.out_width, spec.out_height = ow, oh
-    spec.filter = RESIZE_FILTERS[filter] if isinstance(filter, str) else filter
+    spec.filter = (RESIZE_FILTERS[filter] if isinstance(filter, str) else filter) | (RESIZE_ANTIALIAS if antialias else 0)
     spec.reserved = 0
     return spec
 
@@ -82,12 +86,12 @@ def _rect(crop):
     return Rect(x, y, w, h)
 
 
-def resized_tensor_shape(width, height, size, dtype="f16", downscale=1, filter="bilinear", crop=None):
+def resized_tensor_shape(width, height, size, dtype="f16", downscale=1, filter="bilinear", crop=None, antialias=False):
     """((3, oh, ow), bytes, (ph, pw)) of one WxH image's resized tensor: size = (ow, oh), crop = (x, y, w, h) or None for
     the whole image, (ph, pw) the extent of the block-averaged crop that the filter reads (compeg_resized_tensor_shape;
-    no device needed)."""
+    no device needed).  antialias: as in pack_tensor_resized; its ratio limit (64 either way) is checked here too."""
     spec = _tensor_spec(dtype, downscale, (1, 1, 1), (0, 0, 0), "rgb")
-    resize = _resize_spec(size, filter)
+    resize = _resize_spec(size, filter, antialias)
     rect = _rect(crop) if crop is not None else None
     pw, ph, nbytes = C.c_uint32(), C.c_uint32(), C.c_size_t()
     check(lib.compeg_resized_tensor_shape(C.byref(spec), C.byref(resize), width, height, C.byref(rect) if rect is not None else None,
@@ -426,12 +430,14 @@ class Decoder:
         check(lib.compeg_decoder_pack_tensor(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
 
     def pack_tensor_resized(self, dst, size, crop=None, filter="bilinear", dtype="f16", downscale=1, scale=(1, 1, 1), bias=(0, 0, 0),
-                            order="rgb", hip_stream=0):
+                            order="rgb", hip_stream=0, antialias=False):
         """Extension (compeg_decoder_pack_tensor_resized): like pack_tensor, but crop = (x, y, w, h) of the last decoded image (None: all
         of it) is block-averaged over downscale x downscale pixels and then resized to size = (ow, oh) with filter ("bilinear":
-        half-pixel centres, no antialiasing; "nearest"), giving [3, oh, ow].  Returns without waiting."""
+        half-pixel centres, no antialiasing; "nearest"), giving [3, oh, ow].  antialias=True (bilinear only) widens the filter
+        with the reduction where an axis shrinks, as PIL and torch's interpolate(antialias=True) do; the prefiltered crop may be 64
+        times the output at the most either way.  Returns without waiting."""
         spec = _tensor_spec(dtype, downscale, scale, bias, order)
-        resize = _resize_spec(size, filter)
+        resize = _resize_spec(size, filter, antialias)
         rect = _rect(crop) if crop is not None else None
         addr, nbytes = _device_range(dst)
         check(lib.compeg_decoder_pack_tensor_resized(self._h, C.byref(spec), C.byref(resize), C.byref(rect) if rect is not None else None,
@@ -524,12 +530,13 @@ class Batch:
         check(lib.compeg_batch_pack_tensor(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
 
     def pack_tensor_resized(self, dst, size, crops=None, filter="bilinear", dtype="f16", downscale=1, scale=(1, 1, 1), bias=(0, 0, 0),
-                            order="rgb", hip_stream=0):
+                            order="rgb", hip_stream=0, antialias=False):
         """Extension (compeg_batch_pack_tensor_resized): the last decode's images, of whatever sizes, each block-averaged over downscale x
         downscale pixels and resized to size = (ow, oh), giving [count, 3, oh, ow].  crops: None (whole images), one (x, y, w, h)
-        for every image, or a list with one per image.  Returns without waiting; wait() covers it."""
+        for every image, or a list with one per image.  antialias: as Decoder.pack_tensor_resized has it.  Returns without
+        waiting; wait() covers it."""
         spec = _tensor_spec(dtype, downscale, scale, bias, order)
-        resize = _resize_spec(size, filter)
+        resize = _resize_spec(size, filter, antialias)
         rects = None
         if crops is not None:
             n = self.count()

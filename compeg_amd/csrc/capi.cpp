@@ -166,10 +166,29 @@ int check_resize_spec(const compeg_resize_spec *resize)
     if (resize->out_width == 0u || resize->out_height == 0u || resize->out_width > 65535u || resize->out_height > 65535u)
         return fail(COMPEG_E_INVALID_ARG, ("resize: output size " + std::to_string(resize->out_width) + "x" + std::to_string(resize->out_height) +
                                            " is not within 1..65535 both ways").c_str());
-    if (resize->filter > COMPEG_RESIZE_BILINEAR)
+    // (the low byte is the filter; above it the antialias flag, 0x100, and nothing else)
+    const uint32_t mode = resize->filter & ~uint32_t(COMPEG_RESIZE_ANTIALIAS);
+    if (mode > COMPEG_RESIZE_BILINEAR)
         return fail(COMPEG_E_INVALID_ARG, ("resize: filter " + std::to_string(resize->filter) + " is neither 0 (nearest) nor 1 (bilinear)").c_str());
+    if (resize->filter != mode && mode != COMPEG_RESIZE_BILINEAR)
+        return fail(COMPEG_E_INVALID_ARG, ("resize: filter " + std::to_string(resize->filter) + " asks for antialias (256), which goes with 1 (bilinear) only").c_str());
     if (resize->reserved != 0u)
         return fail(COMPEG_E_INVALID_ARG, "resize: reserved must be 0");
+    return COMPEG_OK;
+}
+
+// The antialias flag's ratio limit for the crop `rect` (already checked) at downscale factor k: the prefiltered extent is
+// at most 64 times the output extent both ways.
+int check_antialias_ratio(const compeg_resize_spec *resize, const compeg_rect &rect, uint32_t k, const std::string &which)
+{
+    if (!(resize->filter & COMPEG_RESIZE_ANTIALIAS))
+        return COMPEG_OK;
+    const uint32_t pw = rect.width / k, ph = rect.height / k;
+    if (uint64_t(pw) > 64u * uint64_t(resize->out_width) || uint64_t(ph) > 64u * uint64_t(resize->out_height))
+        return fail(COMPEG_E_INVALID_ARG, ("resize: " + which + "antialias reduces by 64 at the most either way, " + std::to_string(pw) + "x" + std::to_string(ph) +
+                                           " to " + std::to_string(resize->out_width) + "x" + std::to_string(resize->out_height) +
+                                           " is more: choose a larger downscale")
+                                              .c_str());
     return COMPEG_OK;
 }
 
@@ -1104,6 +1123,8 @@ int compeg_resized_tensor_shape(const compeg_tensor_spec *spec, const compeg_res
         compeg_rect r{};
         if (rc == COMPEG_OK)
             rc = check_crop(crop, width, height, spec->downscale, "", &r);
+        if (rc == COMPEG_OK)
+            rc = check_antialias_ratio(resize, r, spec->downscale, "");
         if (rc != COMPEG_OK)
             return rc;
         if (pre_width)
@@ -1134,6 +1155,8 @@ int compeg_decoder_pack_tensor_resized(compeg_decoder *dec, const compeg_tensor_
         compeg_rect r{};
         rc = check_crop(crop, dec->last_w, dec->last_h, spec->downscale, "", &r);
         if (rc == COMPEG_OK)
+            rc = check_antialias_ratio(resize, r, spec->downscale, "");
+        if (rc == COMPEG_OK)
             rc = check_tensor_destination(device_dst, dst_bytes, size_t(3) * size_t(resize->out_height) * size_t(resize->out_width) * elem, elem);
         if (rc != COMPEG_OK)
             return rc;
@@ -1160,6 +1183,8 @@ int compeg_batch_pack_tensor_resized(compeg_batch *batch, const compeg_tensor_sp
         for (size_t i = 0; i < batch->count; i++) {
             rc = check_crop(crops ? crops + i : nullptr, batch->descs[i].out_w, batch->descs[i].out_h, spec->downscale,
                             "image " + std::to_string(i) + ": ", &rects[i]);
+            if (rc == COMPEG_OK)
+                rc = check_antialias_ratio(resize, rects[i], spec->downscale, "image " + std::to_string(i) + ": ");
             if (rc != COMPEG_OK)
                 return rc;
         }

@@ -1,6 +1,8 @@
 // Host-callable launchers of the gfx950 kernels (kernels.hip).
 #pragma once
 
+#include <vector>
+
 #include <hip/hip_runtime_api.h>
 
 #include "compeg_hip.h"
@@ -119,6 +121,20 @@ constexpr size_t kResizeRecordBytes = 40;
 bool make_resize_record(void *record, const void *src, uint32_t pitch, const compeg_rect &crop, uint32_t k, uint32_t ow, uint32_t oh);
 hipError_t launch_resize_tensor(const void *device_records, uint32_t images, const compeg_tensor_spec &spec,
                                 const compeg_resize_spec &resize, void *dst, hipStream_t stream);
+
+// Antialiased bilinear (resize_kernels.hip, antialias_body.h): the launch's records and axis tables travel as one blob,
+// `images` records of kResizeRecordBytes first, the tables (each distinct axis once) behind them from tables_at on.
+struct AntialiasSource {
+    const void *src; // the image's first pixel, rows pitch bytes apart
+    uint32_t pitch;
+    compeg_rect crop;
+};
+// False: a crop is smaller than k or an axis shrinks by more than the flag takes (the caller has checked both), or the
+// call's tables outgrow the 32 bits their offsets have (thousands of images of different sizes at the largest extents).
+bool make_antialias_blob(std::vector<uint32_t> &blob, size_t &tables_at, const AntialiasSource *sources, uint32_t images, uint32_t k,
+                         uint32_t ow, uint32_t oh);
+hipError_t launch_resize_tensor_antialias(const void *device_blob, size_t tables_at, uint32_t images, const compeg_tensor_spec &spec,
+                                          const compeg_resize_spec &resize, void *dst, hipStream_t stream);
 
 #if defined(CG_AC_STAMPS)
 // diagnostic build: AC-loop cycle counters (kernels_body.h)

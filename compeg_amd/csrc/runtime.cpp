@@ -2317,22 +2317,38 @@ Status compeg_decoder::pack_tensor(const compeg_tensor_spec &spec, void *dst, hi
     return Status{};
 }
 
-// Resized tensor output: the ordering of pack_tensor; the per-image records travel on the pack's own stream in front of
-// the kernel (RecordStage).
+// What a pack says when the antialiased form's records and tables could not be made.  (The C layer has checked the crop
+// and the ratio before, so what is left in practice is the last.)
+static const char kAntialiasNoBlob[] = "tensor: a crop is smaller than the downscale factor or beyond the antialias ratio limit, or this call's "
+                                       "antialias tables outgrow 2^32 words";
+
+// Resized tensor output: the ordering of pack_tensor; the per-image records -- and, antialiased, the axis tables behind
+// them in the same block -- travel on the pack's own stream in front of the kernel (RecordStage).
 Status compeg_decoder::pack_tensor_resized(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_rect &crop,
                                            void *dst, hipStream_t stream)
 {
     CG_HIP(hipSetDevice(gpu->device));
+    const bool antialias = (resize.filter & COMPEG_RESIZE_ANTIALIAS) != 0u;
     alignas(8) uint8_t record[kResizeRecordBytes];
-    if (!make_resize_record(record, out.ptr, uint32_t(out_pitch), crop, spec.downscale, resize.out_width, resize.out_height))
+    std::vector<uint32_t> blob; // antialiased: the record and its two axis tables
+    size_t tables_at = 0;
+    const AntialiasSource source{out.ptr, uint32_t(out_pitch), crop};
+    if (antialias && !make_antialias_blob(blob, tables_at, &source, 1, spec.downscale, resize.out_width, resize.out_height))
+        return Status::error(COMPEG_E_INVALID_ARG, kAntialiasNoBlob);
+    if (!antialias && !make_resize_record(record, out.ptr, uint32_t(out_pitch), crop, spec.downscale, resize.out_width, resize.out_height))
         return Status::error(COMPEG_E_INVALID_ARG, "tensor: the crop is smaller than the downscale factor");
     if (!decode_done)
         CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
     if (decode_pending && stream != last_stream)
         CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
     const void *records = nullptr;
-    CG_TRY(resize_records.upload(record, sizeof record, stream, &records));
-    CG_HIP(launch_resize_tensor(records, 1, spec, resize, dst, stream));
+    if (antialias) {
+        CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &records));
+        CG_HIP(launch_resize_tensor_antialias(records, tables_at, 1, spec, resize, dst, stream));
+    } else {
+        CG_TRY(resize_records.upload(record, sizeof record, stream, &records));
+        CG_HIP(launch_resize_tensor(records, 1, spec, resize, dst, stream));
+    }
     CG_HIP(hipEventRecord(decode_done, stream));
     decode_pending = true;
     last_stream = stream;
@@ -2343,8 +2359,19 @@ Status compeg_batch::pack_tensor_resized(const compeg_tensor_spec &spec, const c
                                          void *dst, hipStream_t stream)
 {
     CG_HIP(hipSetDevice(gpu->device));
-    std::vector<uint8_t> records(count * kResizeRecordBytes);
-    for (size_t i = 0; i < count; i++) {
+    const bool antialias = (resize.filter & COMPEG_RESIZE_ANTIALIAS) != 0u;
+    // (antialiased: the records, then the axis tables, each distinct (extent, output extent) once)
+    std::vector<uint8_t> records(antialias ? 0 : count * kResizeRecordBytes);
+    std::vector<uint32_t> blob;
+    size_t tables_at = 0;
+    if (antialias) {
+        std::vector<AntialiasSource> sources(count);
+        for (size_t i = 0; i < count; i++)
+            sources[i] = AntialiasSource{descs[i].out, descs[i].out_pitch, crops ? crops[i] : compeg_rect{0, 0, descs[i].out_w, descs[i].out_h}};
+        if (!make_antialias_blob(blob, tables_at, sources.data(), uint32_t(count), spec.downscale, resize.out_width, resize.out_height))
+            return Status::error(COMPEG_E_INVALID_ARG, kAntialiasNoBlob);
+    }
+    for (size_t i = 0; i < count && !antialias; i++) {
         const compeg_rect whole{0, 0, descs[i].out_w, descs[i].out_h};
         if (!make_resize_record(records.data() + i * kResizeRecordBytes, descs[i].out, descs[i].out_pitch, crops ? crops[i] : whole, spec.downscale, resize.out_width,
                                resize.out_height))
@@ -2357,8 +2384,14 @@ Status compeg_batch::pack_tensor_resized(const compeg_tensor_spec &spec, const c
         CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
     }
     const void *device_records = nullptr;
-    CG_TRY(resize_records.upload(records.data(), records.size(), stream, &device_records));
-    CG_HIP(launch_resize_tensor(device_records, uint32_t(count), spec, resize, dst, stream));
+    if (antialias)
+        CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &device_records));
+    else
+        CG_TRY(resize_records.upload(records.data(), records.size(), stream, &device_records));
+    if (antialias)
+        CG_HIP(launch_resize_tensor_antialias(device_records, tables_at, uint32_t(count), spec, resize, dst, stream));
+    else
+        CG_HIP(launch_resize_tensor(device_records, uint32_t(count), spec, resize, dst, stream));
     // (no timing events; the next decode on another stream records decode_done on last_stream, behind this)
     last_stream = stream;
     return Status{};

@@ -382,11 +382,32 @@ int compeg_batch_pack_tensor(compeg_batch *batch, const compeg_tensor_spec *spec
  * Every operation is one rounded f32 operation, never fused.  With ow = pw and oh = ph both filters give
  * compeg_*_pack_tensor of the crop, element for element.  No pixel outside the crop is read.
  * Destination: [3][oh][ow] for a decoder, [count][3][oh][ow] for a batch, tight, aligned to its element size.  A
- * batch's images may differ in size; every image gets the same output extent. */
+ * batch's images may differ in size; every image gets the same output extent.
+ *
+ * Antialiased bilinear: filter = COMPEG_RESIZE_BILINEAR | COMPEG_RESIZE_ANTIALIAS (a mode and a flag, as torch's
+ * interpolate has them; the flag goes with no other filter).  Where an axis shrinks the triangle widens with the
+ * reduction, as PIL and torchvision's Resize(antialias=True) have it; prefilter, crop, k, scale, bias, order and the
+ * conversions are unchanged.  Each axis on its own, n its prefiltered extent (pw or ph), o its output extent, x the
+ * output coordinate:
+ *   n <= o (the axis does not shrink): first = i0, count = 2, (w_0, w_1) = (w0, w1) of COMPEG_RESIZE_BILINEAR above
+ *   n > o, in double on the host:  s = double(n) / double(o);  c = s * (x + 0.5)
+ *     lo = max(int64(c - s + 0.5), 0);  hi = min(int64(c + s + 0.5), n)          (conversions truncate toward zero)
+ *     first = lo;  count = hi - lo                                                (at least 1)
+ *     u_t = max(0, 1 - |(t + lo - c + 0.5) * (1.0 / s)|), t = 0 .. count - 1;  total = the sum of u_t in ascending t
+ *     w_t = float(u_t / total)
+ *   tap t reads index min(first + t, n - 1)                (the clamp binds only where the axis does not shrink)
+ *   horizontal first, in f32:  h = P[j][i_0] * wx_0;  then h = h + (P[j][i_t] * wx_t), t = 1 ..
+ *   then vertical over the rows j_t of the y taps in ascending order:  m = h[j_0] * wy_0;  then m = m + (h[j_t] * wy_t)
+ *   v = (m * scale[c]) + bias[c], converted and stored as above.
+ * Every f32 operation is rounded on its own, never fused.  With neither axis shrinking the result is
+ * COMPEG_RESIZE_BILINEAR's, element for element; with ow = pw and oh = ph it is compeg_*_pack_tensor of the crop.
+ * Ratio limit: the flag is rejected (COMPEG_E_INVALID_ARG) when pw > 64 * ow or ph > 64 * oh -- choose a larger
+ * downscale; count is then 129 at the most. */
 #define COMPEG_RESIZE_NEAREST 0
 #define COMPEG_RESIZE_BILINEAR 1
+#define COMPEG_RESIZE_ANTIALIAS 0x100u /* a flag OR-ed into filter; only with COMPEG_RESIZE_BILINEAR */
 typedef struct compeg_resize_spec {
-    uint32_t out_width, out_height, filter, reserved; /* 1..65535 each way; COMPEG_RESIZE_*; reserved = 0 */
+    uint32_t out_width, out_height, filter, reserved; /* 1..65535 each way; COMPEG_RESIZE_* (| the flag); reserved = 0 */
 } compeg_resize_spec;
 typedef struct compeg_rect {
     uint32_t x, y, width, height;
@@ -394,7 +415,8 @@ typedef struct compeg_rect {
 /* No device needed: validates, and reports the prefiltered crop's extent (each output optional) and the byte count of
  * one image's tensor (3 * oh * ow * element size) for a WxH source.  COMPEG_E_INVALID_ARG for what compeg_tensor_shape
  * rejects and for: an output extent of 0 or above 65535, an unknown filter, reserved != 0, a crop with a side of 0 or
- * one that leaves the image, a crop (or image) smaller than downscale either way. */
+ * one that leaves the image, a crop (or image) smaller than downscale either way, COMPEG_RESIZE_ANTIALIAS with another
+ * filter than bilinear or beyond its ratio limit. */
 int compeg_resized_tensor_shape(const compeg_tensor_spec *spec, const compeg_resize_spec *resize, uint32_t width,
                                 uint32_t height, const compeg_rect *crop, uint32_t *pre_width, uint32_t *pre_height,
                                 size_t *bytes_per_image);

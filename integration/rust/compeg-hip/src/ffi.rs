@@ -74,6 +74,8 @@ pub const COMPEG_TENSOR_RGB: u32 = 0;
 pub const COMPEG_TENSOR_BGR: u32 = 1;
 pub const COMPEG_RESIZE_NEAREST: u32 = 0;
 pub const COMPEG_RESIZE_BILINEAR: u32 = 1;
+/// A flag OR-ed into `compeg_resize_spec::filter`; only with `COMPEG_RESIZE_BILINEAR`.
+pub const COMPEG_RESIZE_ANTIALIAS: u32 = 0x100;
 
 extern "C" {
     pub fn compeg_last_error() -> *const c_char;

@@ -120,11 +120,15 @@ impl TensorSpec {
     }
 }
 
-/// Filter of a resized pack (`COMPEG_RESIZE_*`).
+/// Filter of a resized pack (`COMPEG_RESIZE_*`).  `BilinearAntialias` is `COMPEG_RESIZE_BILINEAR |
+/// COMPEG_RESIZE_ANTIALIAS`: where an axis shrinks the filter widens with the reduction, as PIL and torch's
+/// `interpolate(antialias=True)` do; where none shrinks it is `Bilinear` element for element.  The block-averaged crop
+/// may then be 64 times the output at the most either way.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum ResizeFilter {
     Nearest = 0,
     Bilinear = 1,
+    BilinearAntialias = (ffi::COMPEG_RESIZE_BILINEAR | ffi::COMPEG_RESIZE_ANTIALIAS) as isize,
 }
 
 /// A crop in pixels (`compeg_rect`).
@@ -132,7 +136,7 @@ pub type Rect = ffi::compeg_rect;
 
 /// The fixed output extent of `Decoder::pack_tensor_resized` / `Batch::pack_tensor_resized` (extension; compeg_hip.h,
 /// "Resized tensor output"): the crop is block-averaged as `TensorSpec::downscale` says, then resized to `width` x
-/// `height` -- bilinear with half-pixel centres and no antialiasing, or nearest.
+/// `height` -- bilinear with half-pixel centres (antialiased or not), or nearest.
 #[derive(Clone, Copy, Debug)]
 pub struct ResizeSpec {
     pub width: u32,
@@ -143,6 +147,13 @@ pub struct ResizeSpec {
 impl ResizeSpec {
     pub fn new(width: u32, height: u32) -> Self {
         ResizeSpec { width, height, filter: ResizeFilter::Bilinear }
+    }
+
+    /// The antialias switch: the same extent with `BilinearAntialias` (on) or `Bilinear` (off).  The flag goes with no
+    /// other filter, so this replaces `Nearest` too.
+    pub fn antialias(mut self, on: bool) -> Self {
+        self.filter = if on { ResizeFilter::BilinearAntialias } else { ResizeFilter::Bilinear };
+        self
     }
 
     fn raw(&self) -> ffi::compeg_resize_spec {

@@ -12,6 +12,11 @@ clock primed as bench.py does it.  Needs the card: there is no CPU path.  Writes
 profiles/tensor_resize.txt) and prints it.
 
     python tools/resize_probe.py [--batch 256] [--distinct 16] [--reps 10] [--out profiles/tensor_resize.txt]
+
+The antialias arm (--antialias; default table profiles/tensor_resize_antialias.txt): resident batches of 1920x1080 and
+of 3840x2160 -> 224x224 in f16, at k = 1 and at the largest k that leaves both axes shrinking.  Per configuration,
+launch by launch in turn and by HIP events on one stream: the antialiased pack, the plain bilinear pack at the same
+shapes, and the decode of the same batch, which is what the pack follows in a pipeline.
 """
 import argparse
 import os
@@ -34,14 +39,79 @@ CONFIGS = (("4K -> 224x224 f16 k=8", ((3840, 2160),), (224, 224), "f16", 8),
            ("mixed -> 224x224 f16 k=1", ((1920, 1080), (1280, 720), (960, 720), (640, 360)), (224, 224), "f16", 1))
 
 
+# the antialias arm: (name, (width, height), output size, element type, k)
+ANTIALIAS_CONFIGS = (("1080p -> 224x224 f16 k=1", (1920, 1080), (224, 224), "f16", 1),
+                     ("1080p -> 224x224 f16 k=4", (1920, 1080), (224, 224), "f16", 4),
+                     ("4K -> 224x224 f16 k=1", (3840, 2160), (224, 224), "f16", 1),
+                     ("4K -> 224x224 f16 k=8", (3840, 2160), (224, 224), "f16", 8))
+
+
+def antialias_arm(args, torch, compeg_amd, images_of, resident, gpu, stream):
+    """The table of the antialias arm, as text."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import antialias_reference as ar   # the header's contract in numpy
+    n, handle = args.batch, stream.cuda_stream
+    scale = [1.0 / (255.0 * s) for s in STD]
+    bias = [-m / s for m, s in zip(MEAN, STD)]
+    lines = [f"antialiased resized tensor output: {n} resident 4:2:2 DRI=4 frames per configuration; {gpu.name()}",
+             f"antialias = Batch.pack_tensor_resized(antialias=True), bilinear = the same call without the flag, decode = Batch.decode of the same "
+             f"batch; HIP events on one stream, launch by launch in turn; median of {args.reps} (min .. max)",
+             f"{'configuration':<26} {'antialias ms':>26} {'bilinear ms':>24} {'decode ms':>24} {'antialias/decode':>16}"]
+    dearer = []
+    for name, (w, h), (ow, oh), dtype, k in ANTIALIAS_CONFIGS:
+        items = images_of(w, h)
+        batch = resident([items[i % len(items)] for i in range(n)])
+        dst = torch.empty((n, 3, oh, ow), dtype=torch.float16, device="cuda")
+        plain = torch.empty((n, 3, oh, ow), dtype=torch.float16, device="cuda")
+
+        def pack(out, antialias):
+            batch.pack_tensor_resized(out, (ow, oh), dtype=dtype, downscale=k, scale=scale, bias=bias, hip_stream=handle, antialias=antialias)
+
+        with torch.cuda.stream(stream):
+            for _ in range(2):   # warm-up: code objects, the staging blocks
+                pack(dst, True)
+                pack(plain, False)
+                batch.decode(handle)
+            stream.synchronize()
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < PRIME_SECONDS:
+                batch.decode(handle)
+                batch.wait()
+            ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(args.reps)]
+            for e in ev:
+                e[0].record(stream)
+                pack(dst, True)
+                e[1].record(stream)
+                pack(plain, False)
+                e[2].record(stream)
+                batch.decode(handle)
+                e[3].record(stream)
+            stream.synchronize()
+        t = [[e[i].elapsed_time(e[i + 1]) for e in ev] for i in range(3)]
+        med = [statistics.median(x) for x in t]
+        # (slot 0 against the contract on the host: what is timed is what the header defines)
+        wrong = int((ar.expected(batch.read_output(0), (ow, oh), k, dtype, scale, bias) != dst[0].cpu().numpy()).sum())
+        cells = " ".join(f"{m:9.3f} ({min(x):.3f} .. {max(x):.3f})" for m, x in zip(med, t))
+        lines.append(f"{name:<26} {cells} {med[0] / med[2]:16.2f}   slot 0: {wrong} elements off the contract")
+        if med[0] > med[2]:
+            dearer.append(name)
+        del dst, plain, batch
+        torch.cuda.empty_cache()
+    lines.append("antialiased pack dearer than the decode it follows: " + ("; ".join(dearer) if dearer else "none"))
+    return "\n".join(lines) + "\n"
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=256)
     p.add_argument("--distinct", type=int, default=16, help="distinct synthetic frames per size (timings do not depend on the content)")
     p.add_argument("--reps", type=int, default=10, help="timed launches per configuration, of the pack and of the chain in turn")
     p.add_argument("--threads", type=int, default=16)
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "tensor_resize.txt"))
+    p.add_argument("--out", default=None, help="default: profiles/tensor_resize.txt, or profiles/tensor_resize_antialias.txt with --antialias")
+    p.add_argument("--antialias", action="store_true", help="the antialias arm instead of the table against the chain")
     args = p.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "tensor_resize_antialias.txt" if args.antialias else "tensor_resize.txt")
 
     import torch
     import torch.nn.functional as F
@@ -72,6 +142,14 @@ def main():
         batch.decode(handle)
         batch.wait()
         return batch
+
+    if args.antialias:
+        text = antialias_arm(args, torch, compeg_amd, images_of, resident, gpu, stream)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text)
+        print(text, end="")
+        return
 
     lines = [f"resized tensor output: {n} resident 4:2:2 DRI=4 frames per configuration, decoded once; {gpu.name()}",
              f"resized = Batch.pack_tensor_resized alone, HIP events on its stream; chain = pack_tensor(f32, k) -> F.interpolate(bilinear) -> "
