@@ -18,11 +18,12 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
-                   LIB_PATH, METADATA_BYTES, Error, Rect, ResizeSpec, TensorSpec, check, lib)
+                   LIB_PATH, METADATA_BYTES, Error, Rect, Region, ResizeSpec, TensorSpec, check, lib)
 
 __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Texture", "Error", "HostBuffer", "JpegList",
            "host_register", "host_unregister", "version", "LIB_PATH", "tensor_shape", "TENSOR_DTYPES", "TENSOR_ORDERS",
-           "resized_tensor_shape", "RESIZE_FILTERS", "ResizeSpec", "Rect"]
+           "resized_tensor_shape", "RESIZE_FILTERS", "ResizeSpec", "Rect", "Region", "FIT_ALIGNS", "region_fit",
+           "region_tensor_shape"]
 
 
 # compeg_decoder_last_kernel / compeg_batch_last_kernel (include/compeg_hip.h: COMPEG_KERNEL_*)
@@ -96,6 +97,55 @@ def resized_tensor_shape(width, height, size, dtype="f16", downscale=1, filter="
     pw, ph, nbytes = C.c_uint32(), C.c_uint32(), C.c_size_t()
     check(lib.compeg_resized_tensor_shape(C.byref(spec), C.byref(resize), width, height, C.byref(rect) if rect is not None else None,
                                           C.byref(pw), C.byref(ph), C.byref(nbytes)))
+    return (3, resize.out_height, resize.out_width), nbytes.value, (ph.value, pw.value)
+
+
+# Region tensor output (include/compeg_hip.h: COMPEG_FIT_*): placements by name
+FIT_ALIGNS = {"center": 0, "top_left": 1}
+
+
+def _region(region):
+    """compeg_region from (image, src or None, dst or None), rectangles as (x, y, w, h); or a Region as it is."""
+    if isinstance(region, Region):
+        return region
+    image, src, dst = region
+    r = Region()
+    r.image, r.reserved = image, 0
+    r.src = src if isinstance(src, Rect) else (_rect(src) if src is not None else Rect(0, 0, 0, 0))
+    r.dst = dst if isinstance(dst, Rect) else (_rect(dst) if dst is not None else Rect(0, 0, 0, 0))
+    return r
+
+
+def _regions(regions):
+    regions = list(regions)
+    return (Region * max(len(regions), 1))(*[_region(r) for r in regions]), len(regions)
+
+
+def _pad(pad):
+    return (C.c_float * 3)(*[float(x) for x in pad]) if pad is not None else None
+
+
+def region_fit(src_size, out_size, align="center"):
+    """(dx, dy, dw, dh): the rectangle of out_size = (ow, oh) that a crop of src_size = (w, h) pixels fills when it is
+    fitted with its aspect ratio kept, centred or ("top_left") at the origin (compeg_region_fit; no device needed)."""
+    if isinstance(align, str) and align not in FIT_ALIGNS:
+        raise Error(f"unknown fit align {align!r} (one of {', '.join(FIT_ALIGNS)})")
+    rect = Rect()
+    check(lib.compeg_region_fit(src_size[0], src_size[1], out_size[0], out_size[1], FIT_ALIGNS[align] if isinstance(align, str) else align,
+                                C.byref(rect)))
+    return rect.x, rect.y, rect.width, rect.height
+
+
+def region_tensor_shape(width, height, size, region=None, dtype="f16", downscale=1, filter="bilinear", antialias=False):
+    """((3, oh, ow), bytes, (ph, pw)) of one slot of a region pack: region = (image, src or None, dst or None) of a WxH
+    image (None: the whole image into the whole output), checked as the pack calls check it, all but the image index
+    (compeg_region_tensor_shape; no device needed).  The antialias limit is taken against dst's extent."""
+    spec = _tensor_spec(dtype, downscale, (1, 1, 1), (0, 0, 0), "rgb")
+    resize = _resize_spec(size, filter, antialias)
+    r = _region(region) if region is not None else None
+    pw, ph, nbytes = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    check(lib.compeg_region_tensor_shape(C.byref(spec), C.byref(resize), width, height, C.byref(r) if r is not None else None,
+                                         C.byref(pw), C.byref(ph), C.byref(nbytes)))
     return (3, resize.out_height, resize.out_width), nbytes.value, (ph.value, pw.value)
 
 
@@ -443,6 +493,19 @@ class Decoder:
         check(lib.compeg_decoder_pack_tensor_resized(self._h, C.byref(spec), C.byref(resize), C.byref(rect) if rect is not None else None,
                                                      C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
 
+    def pack_tensor_regions(self, dst, size, regions, pad=(0, 0, 0), filter="bilinear", dtype="f16", downscale=1, scale=(1, 1, 1),
+                            bias=(0, 0, 0), order="rgb", hip_stream=0, antialias=False):
+        """Extension (compeg_decoder_pack_tensor_regions): regions = [(0, src or None, dst or None), ...] of the last decoded image
+        into [len(regions), 3, oh, ow]: crop src is resized as pack_tensor_resized does it into rectangle dst of its slot
+        (region_fit gives the letterbox's), the rest of the slot is pad (R, G, B on the pixel scale) put through scale and
+        bias.  Returns without waiting, like pack_tensor."""
+        spec = _tensor_spec(dtype, downscale, scale, bias, order)
+        resize = _resize_spec(size, filter, antialias)
+        list_, n = _regions(regions)
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_decoder_pack_tensor_regions(self._h, C.byref(spec), C.byref(resize), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
+                                                     C.c_void_p(hip_stream)))
+
     def read_coefficients(self, total_dus):
         out = np.empty(total_dus * 32, dtype=np.int32)
         check(lib.compeg_decoder_read_coefficients(self._h, out.ctypes.data, out.size))
@@ -547,6 +610,18 @@ class Batch:
             rects = (Rect * max(n, 1))(*[c if isinstance(c, Rect) else _rect(c) for c in crops])
         addr, nbytes = _device_range(dst)
         check(lib.compeg_batch_pack_tensor_resized(self._h, C.byref(spec), C.byref(resize), rects, C.c_void_p(addr), nbytes,
+                                                   C.c_void_p(hip_stream)))
+
+    def pack_tensor_regions(self, dst, size, regions, pad=(0, 0, 0), filter="bilinear", dtype="f16", downscale=1, scale=(1, 1, 1),
+                            bias=(0, 0, 0), order="rgb", hip_stream=0, antialias=False):
+        """Extension (compeg_batch_pack_tensor_regions): regions = [(image, src or None, dst or None), ...] over the last decode's
+        images -- any of them any number of times, in any order -- into [len(regions), 3, oh, ow], as
+        Decoder.pack_tensor_regions has it.  Returns without waiting; wait() covers it."""
+        spec = _tensor_spec(dtype, downscale, scale, bias, order)
+        resize = _resize_spec(size, filter, antialias)
+        list_, n = _regions(regions)
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_batch_pack_tensor_regions(self._h, C.byref(spec), C.byref(resize), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
                                                    C.c_void_p(hip_stream)))
 
     def algorithmic_bytes(self):

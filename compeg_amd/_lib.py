@@ -38,6 +38,12 @@ class Rect(C.Structure):
     _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32)]
 
 
+class Region(C.Structure):
+    """compeg_region (include/compeg_hip.h, "Region tensor output"): which crop of which image fills which rectangle of
+    its output slot; an all-zero src is the whole image, an all-zero dst the whole output."""
+    _fields_ = [("image", C.c_uint32), ("reserved", C.c_uint32), ("src", Rect), ("dst", Rect)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -120,6 +126,10 @@ def _load():
         "compeg_resized_tensor_shape": (i, [C.POINTER(TensorSpec), C.POINTER(ResizeSpec), u32, u32, C.POINTER(Rect), pu32, pu32, psz]),
         "compeg_decoder_pack_tensor_resized": (i, [vp, C.POINTER(TensorSpec), C.POINTER(ResizeSpec), C.POINTER(Rect), vp, sz, vp]),
         "compeg_batch_pack_tensor_resized": (i, [vp, C.POINTER(TensorSpec), C.POINTER(ResizeSpec), C.POINTER(Rect), vp, sz, vp]),
+        "compeg_region_fit": (i, [u32, u32, u32, u32, C.c_uint, C.POINTER(Rect)]),
+        "compeg_region_tensor_shape": (i, [C.POINTER(TensorSpec), C.POINTER(ResizeSpec), u32, u32, C.POINTER(Region), pu32, pu32, psz]),
+        "compeg_decoder_pack_tensor_regions": (i, [vp, C.POINTER(TensorSpec), C.POINTER(ResizeSpec), C.POINTER(Region), sz, C.POINTER(C.c_float), vp, sz, vp]),
+        "compeg_batch_pack_tensor_regions": (i, [vp, C.POINTER(TensorSpec), C.POINTER(ResizeSpec), C.POINTER(Region), sz, C.POINTER(C.c_float), vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("COMPEG_LIB") and not hasattr(L, name):

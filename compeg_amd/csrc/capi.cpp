@@ -212,6 +212,69 @@ int check_crop(const compeg_rect *crop, uint32_t width, uint32_t height, uint32_
     return COMPEG_OK;
 }
 
+// One region of a call whose image is WxH, into whole rectangles: `out` is the region with src and dst resolved.
+// `which`: what the messages call it ("region 3: ").  The antialias limit is taken against the inner extent.
+int check_region(const compeg_region *region, const compeg_tensor_spec *spec, const compeg_resize_spec *resize, uint32_t width,
+                 uint32_t height, const std::string &which, compeg_region *out)
+{
+    const compeg_region whole{};
+    const compeg_region &g = region ? *region : whole;
+    if (g.reserved != 0u)
+        return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "reserved must be 0").c_str());
+    const bool src_whole = !g.src.x && !g.src.y && !g.src.width && !g.src.height;
+    const bool dst_whole = !g.dst.x && !g.dst.y && !g.dst.width && !g.dst.height;
+    compeg_region r{};
+    r.image = g.image;
+    int rc = check_crop(src_whole ? nullptr : &g.src, width, height, spec->downscale, which, &r.src);
+    if (rc != COMPEG_OK)
+        return rc;
+    r.dst = dst_whole ? compeg_rect{0, 0, resize->out_width, resize->out_height} : g.dst;
+    const std::string text = std::to_string(r.dst.width) + "x" + std::to_string(r.dst.height);
+    if (r.dst.width == 0u || r.dst.height == 0u)
+        return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "dst " + text + " has a side of 0").c_str());
+    // (64 bits: x + width must not wrap)
+    if (uint64_t(r.dst.x) + r.dst.width > resize->out_width || uint64_t(r.dst.y) + r.dst.height > resize->out_height)
+        return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "dst " + text + " at (" + std::to_string(r.dst.x) + ", " + std::to_string(r.dst.y) +
+                                           ") leaves the " + std::to_string(resize->out_width) + "x" + std::to_string(resize->out_height) + " output").c_str());
+    compeg_resize_spec inner = *resize;
+    inner.out_width = r.dst.width;
+    inner.out_height = r.dst.height;
+    rc = check_antialias_ratio(&inner, r.src, spec->downscale, which);
+    if (rc != COMPEG_OK)
+        return rc;
+    *out = r;
+    return COMPEG_OK;
+}
+
+// What both region packs check before they look at their object: the specs, the list, the pad.
+int check_region_call(const compeg_tensor_spec *spec, const compeg_resize_spec *resize, const compeg_region *regions, size_t count,
+                      const float *pad, size_t *elem_bytes)
+{
+    int rc = check_tensor_spec(spec, elem_bytes);
+    if (rc == COMPEG_OK)
+        rc = check_resize_spec(resize);
+    if (rc != COMPEG_OK)
+        return rc;
+    if (!regions)
+        return fail(COMPEG_E_INVALID_ARG, "tensor: regions is NULL");
+    if (count == 0)
+        return fail(COMPEG_E_INVALID_ARG, "tensor: a region count of 0");
+    for (int c = 0; pad && c < 3; c++)
+        if (!std::isfinite(pad[c]))
+            return fail(COMPEG_E_INVALID_ARG, ("tensor: pad of channel " + std::to_string(c) + " is not finite").c_str());
+    return COMPEG_OK;
+}
+
+// Bytes of `count` slots, or false where size_t does not hold them.
+bool region_tensor_bytes(const compeg_resize_spec *resize, size_t elem, size_t count, size_t *bytes)
+{
+    const size_t slot = size_t(3) * size_t(resize->out_height) * size_t(resize->out_width) * elem;
+    if (count > SIZE_MAX / slot)
+        return false;
+    *bytes = slot * count;
+    return true;
+}
+
 } // namespace
 
 extern "C" {
@@ -1192,6 +1255,141 @@ int compeg_batch_pack_tensor_resized(compeg_batch *batch, const compeg_tensor_sp
         if (rc != COMPEG_OK)
             return rc;
         Status s = batch->pack_tensor_resized(*spec, *resize, rects.data(), device_dst, hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream);
+        return s.ok() ? ok() : fail(s);
+    });
+}
+
+/* ---- Region tensor output -------------------------------------------------- */
+
+int compeg_region_fit(uint32_t src_width, uint32_t src_height, uint32_t out_width, uint32_t out_height, unsigned align, compeg_rect *dst)
+{
+    return guarded([&] {
+        if (!dst)
+            return fail(COMPEG_E_INVALID_ARG, "dst is NULL");
+        if (src_width == 0u || src_height == 0u)
+            return fail(COMPEG_E_INVALID_ARG, ("region fit: a source extent of " + std::to_string(src_width) + "x" + std::to_string(src_height) +
+                                               " has a side of 0").c_str());
+        if (out_width == 0u || out_height == 0u || out_width > 65535u || out_height > 65535u)
+            return fail(COMPEG_E_INVALID_ARG, ("region fit: output size " + std::to_string(out_width) + "x" + std::to_string(out_height) +
+                                               " is not within 1..65535 both ways").c_str());
+        if (align > COMPEG_FIT_TOP_LEFT)
+            return fail(COMPEG_E_INVALID_ARG, ("region fit: align " + std::to_string(align) + " is neither 0 (center) nor 1 (top left)").c_str());
+        // (a source side is below 2^32, an output side below 2^16: every product below 2^50)
+        const uint64_t sw = src_width, sh = src_height, ow = out_width, oh = out_height;
+        uint64_t dw, dh;
+        if (ow * sh <= oh * sw) {
+            dw = ow;
+            dh = (2u * sh * ow + sw) / (2u * sw);
+            dh = dh < 1u ? 1u : (dh > oh ? oh : dh);
+        } else {
+            dh = oh;
+            dw = (2u * sw * oh + sh) / (2u * sh);
+            dw = dw < 1u ? 1u : (dw > ow ? ow : dw);
+        }
+        const bool center = align == COMPEG_FIT_CENTER;
+        *dst = compeg_rect{center ? uint32_t((ow - dw) / 2u) : 0u, center ? uint32_t((oh - dh) / 2u) : 0u, uint32_t(dw), uint32_t(dh)};
+        return ok();
+    });
+}
+
+int compeg_region_tensor_shape(const compeg_tensor_spec *spec, const compeg_resize_spec *resize, uint32_t width, uint32_t height,
+                               const compeg_region *region, uint32_t *pre_width, uint32_t *pre_height, size_t *bytes_per_slot)
+{
+    return guarded([&] {
+        size_t elem = 0;
+        int rc = check_tensor_spec(spec, &elem);
+        if (rc == COMPEG_OK)
+            rc = check_resize_spec(resize);
+        compeg_region r{};
+        if (rc == COMPEG_OK)
+            rc = check_region(region, spec, resize, width, height, "", &r);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (pre_width)
+            *pre_width = r.src.width / spec->downscale;
+        if (pre_height)
+            *pre_height = r.src.height / spec->downscale;
+        if (bytes_per_slot)
+            *bytes_per_slot = size_t(3) * size_t(resize->out_height) * size_t(resize->out_width) * elem;
+        return ok();
+    });
+}
+
+int compeg_decoder_pack_tensor_regions(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_resize_spec *resize,
+                                       const compeg_region *regions, size_t count, const float *pad, void *device_dst, size_t dst_bytes,
+                                       void *hip_stream)
+{
+    return guarded([&] {
+        // (what does not depend on the object first: it is checked where no device is)
+        size_t elem = 0, bytes = 0;
+        int rc = check_region_call(spec, resize, regions, count, pad, &elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (!dec)
+            return fail(COMPEG_E_INVALID_ARG, "dec is NULL");
+        if (!dec->have_last || !dec->out.ptr)
+            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
+        if (!region_tensor_bytes(resize, elem, count, &bytes))
+            return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
+        // (the launch's limits and the destination before the list is copied: nothing is allocated for a count no call takes)
+        if (count > 0xffffffffull || !compeg::region_grid_fits(uint32_t(count), *spec, *resize))
+            return fail(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
+        rc = check_tensor_destination(device_dst, dst_bytes, bytes, elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        // (the copy of the caller's list: src and dst as whole rectangles)
+        std::vector<compeg_region> list(count);
+        for (size_t r = 0; r < count; r++) {
+            const std::string which = "region " + std::to_string(r) + ": ";
+            if (regions[r].image != 0u)
+                return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "image " + std::to_string(regions[r].image) + ", a decoder has image 0 only").c_str());
+            rc = check_region(regions + r, spec, resize, dec->last_w, dec->last_h, which, &list[r]);
+            if (rc != COMPEG_OK)
+                return rc;
+        }
+        const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
+        Status s = dec->pack_tensor_regions(*spec, *resize, list.data(), count, pad_copy, device_dst,
+                                            hip_stream ? static_cast<hipStream_t>(hip_stream) : dec->gpu->stream);
+        return s.ok() ? ok() : fail(s);
+    });
+}
+
+int compeg_batch_pack_tensor_regions(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_resize_spec *resize,
+                                     const compeg_region *regions, size_t count, const float *pad, void *device_dst, size_t dst_bytes,
+                                     void *hip_stream)
+{
+    return guarded([&] {
+        // (what does not depend on the object first: it is checked where no device is)
+        size_t elem = 0, bytes = 0;
+        int rc = check_region_call(spec, resize, regions, count, pad, &elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (!batch)
+            return fail(COMPEG_E_INVALID_ARG, "batch is NULL");
+        if (!batch->count || !batch->output_decoded)
+            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
+        if (!region_tensor_bytes(resize, elem, count, &bytes))
+            return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
+        // (the launch's limits and the destination before the list is copied: nothing is allocated for a count no call takes)
+        if (count > 0xffffffffull || !compeg::region_grid_fits(uint32_t(count), *spec, *resize))
+            return fail(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
+        rc = check_tensor_destination(device_dst, dst_bytes, bytes, elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        std::vector<compeg_region> list(count);
+        for (size_t r = 0; r < count; r++) {
+            const std::string which = "region " + std::to_string(r) + ": ";
+            const uint32_t i = regions[r].image;
+            if (i >= batch->count)
+                return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "image " + std::to_string(i) + " is beyond the batch's " +
+                                                   std::to_string(batch->count) + " images").c_str());
+            rc = check_region(regions + r, spec, resize, batch->descs[i].out_w, batch->descs[i].out_h, which, &list[r]);
+            if (rc != COMPEG_OK)
+                return rc;
+        }
+        const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
+        Status s = batch->pack_tensor_regions(*spec, *resize, list.data(), count, pad_copy, device_dst,
+                                              hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream);
         return s.ok() ? ok() : fail(s);
     });
 }

@@ -7,6 +7,7 @@
 
 #include "compeg_hip.h"
 #include "device_types.h"
+#include "region_types.h"
 
 namespace compeg {
 
@@ -135,6 +136,20 @@ bool make_antialias_blob(std::vector<uint32_t> &blob, size_t &tables_at, const A
                          uint32_t ow, uint32_t oh);
 hipError_t launch_resize_tensor_antialias(const void *device_blob, size_t tables_at, uint32_t images, const compeg_tensor_spec &spec,
                                           const compeg_resize_spec &resize, void *dst, hipStream_t stream);
+
+// Region tensor output (region_kernels.hip, region_body.h): `slots` records of kRegionRecordBytes and, antialiased, the
+// axis tables behind them from tables_at on, as one blob.  A slot's record says which crop of which image fills which
+// rectangle of the slot (region_types.h: RegionSource); the rest of the slot is the pad value.
+constexpr size_t kRegionRecordBytes = 48;
+// filter: compeg_resize_spec's.  False: a crop is smaller than k or an axis shrinks by more than the antialias flag
+// takes (the caller has checked both), or the call's tables outgrow the 32 bits their offsets have.
+bool make_region_blob(std::vector<uint32_t> &blob, size_t &tables_at, const RegionSource *sources, uint32_t slots, uint32_t k,
+                      uint32_t filter);
+// Whether the launch's grid fits (the planners' limits of the resized packs, `slots` for images).
+bool region_grid_fits(uint32_t slots, const compeg_tensor_spec &spec, const compeg_resize_spec &resize);
+// pad: three values on the pixel scale by source channel (R, G, B), or null for zeros.
+hipError_t launch_region_tensor(const void *device_blob, size_t tables_at, uint32_t slots, const compeg_tensor_spec &spec,
+                                const compeg_resize_spec &resize, const float *pad, void *dst, hipStream_t stream);
 
 #if defined(CG_AC_STAMPS)
 // diagnostic build: AC-loop cycle counters (kernels_body.h)

@@ -155,6 +155,10 @@ struct compeg_decoder {
     compeg::RecordStage resize_records;
     compeg::Status pack_tensor_resized(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_rect &crop,
                                        void *dst, hipStream_t stream);
+    // Region tensor output: `count` slots, each a crop of the last image into a rectangle of its slot; src and dst are
+    // whole rectangles by now, and inside the image and the output (checked by the caller, like specs, pad and dst)
+    compeg::Status pack_tensor_regions(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_region *regions,
+                                       size_t count, const float *pad, void *dst, hipStream_t stream);
     compeg::Status check_scan_result(bool &fell_back);
     compeg::Status preprocess_on_device(const compeg::ImageData &img, hipStream_t stream, uint32_t &nwords,
                                         uint32_t &nstarts, uint32_t &span, bool &fell_back, size_t blob_bytes,
@@ -255,4 +259,8 @@ struct compeg_batch {
     compeg::RecordStage resize_records;
     compeg::Status pack_tensor_resized(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_rect *crops,
                                        void *dst, hipStream_t stream);
+    // Region tensor output: `count` slots, each a crop of image regions[r].image; src and dst are whole rectangles by
+    // now, and inside their image and the output (checked by the caller, like specs, pad and dst)
+    compeg::Status pack_tensor_regions(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_region *regions,
+                                       size_t count, const float *pad, void *dst, hipStream_t stream);
 };

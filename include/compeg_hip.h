@@ -430,6 +430,67 @@ int compeg_batch_pack_tensor_resized(compeg_batch *batch, const compeg_tensor_sp
                                      const compeg_resize_spec *resize, const compeg_rect *crops, void *device_dst,
                                      size_t dst_bytes, void *hip_stream);
 
+/* ---- Region tensor output (extension) ----------------------------------------
+ * compeg_*_pack_tensor_resized above takes one crop per image, gives slot i to image i and fills the whole ow x oh
+ * output with the resized crop.  These calls take a list of regions instead.  A region says which image, which crop
+ * of it, and which rectangle of its output slot the resized crop fills; everything outside that rectangle is a pad
+ * value.  So M crops from whichever frames hold them become one [M][3][oh][ow] batch, and a frame is fitted into a
+ * model's input with its aspect ratio kept (a letterbox), in one hand-written kernel.  Nothing else changes.
+ *
+ * Destination: [count][3][oh][ow], tight, aligned to its element size; count is the number of regions, not of images:
+ * an image may appear any number of times, in any order, or not at all.
+ * Inside the inner rectangle: slot r has the inner rectangle (dx, dy, dw, dh) = regions[r].dst.  Element (c, y, x)
+ * with dx <= x < dx + dw and dy <= y < dy + dh equals element (c, y - dy, x - dx) of compeg_*_pack_tensor_resized of
+ * image regions[r].image with the crop regions[r].src, the output extent dw x dh and the same spec, filter and flag,
+ * bit for bit: the prefilter, ratios, taps, tables and summation order above apply with (ow, oh) := (dw, dh).  No pixel
+ * outside the crop is read.
+ * Outside the inner rectangle: every other element of plane c is
+ *   v = (pad[ch] * scale[c]) + bias[c],  ch the source channel of plane c under order (c, or 2 - c)
+ * two f32 operations, each rounded, never fused; converted and stored like every other element.  pad: three floats on
+ * the 0..255 pixel scale, indexed by source channel (R, G, B); NULL: zeros; any finite value is allowed.
+ * Writes: every element of every slot is written exactly once; no byte outside the tensor is written.
+ * Antialiasing: COMPEG_RESIZE_ANTIALIAS keeps its ratio limit, against the inner extent: a region is rejected when
+ * pw > 64 * dw or ph > 64 * dh.  Axis tables are built once per distinct (n, o) of the call. */
+typedef struct compeg_region {
+    uint32_t image;    /* index into the batch's last upload; 0 for a decoder */
+    uint32_t reserved; /* 0 */
+    compeg_rect src;   /* crop inside the image; all four fields 0: the whole image */
+    compeg_rect dst;   /* rectangle inside ow x oh that the resized crop fills; all four 0: the whole output */
+} compeg_region;       /* 40 bytes */
+#define COMPEG_FIT_CENTER 0
+#define COMPEG_FIT_TOP_LEFT 1
+/* No device needed: the inner rectangle that fits a src_width x src_height crop (its pixel extent, before downscale)
+ * into out_width x out_height with its aspect ratio kept, in 64-bit integers:
+ *   out_width * src_height <= out_height * src_width:
+ *     dw = out_width,  dh = (2 * src_height * out_width + src_width) / (2 * src_width), clamped to 1..out_height
+ *   otherwise:
+ *     dh = out_height, dw = (2 * src_width * out_height + src_height) / (2 * src_height), clamped to 1..out_width
+ *   COMPEG_FIT_CENTER: dx = (out_width - dw) / 2, dy = (out_height - dh) / 2;  COMPEG_FIT_TOP_LEFT: dx = dy = 0
+ * (3840x2160 into 640x640: (0, 140, 640, 360); 330x70 into 48x40: (0, 15, 48, 10)).  COMPEG_E_INVALID_ARG for a source
+ * extent of 0, an output extent of 0 or above 65535, an unknown align, dst NULL. */
+int compeg_region_fit(uint32_t src_width, uint32_t src_height, uint32_t out_width, uint32_t out_height,
+                      unsigned align, compeg_rect *dst);
+/* No device needed: validates one region (NULL: the whole image into the whole output) of a WxH image as the pack calls
+ * do, all but its image index, and reports the prefiltered crop's extent (each output optional) and the byte count of
+ * one slot (3 * oh * ow * element size).  COMPEG_E_INVALID_ARG for everything compeg_resized_tensor_shape rejects, the
+ * antialias limit taken against the inner extent, and for: reserved != 0, a src or dst with a side of 0 that is not the
+ * all-zero rectangle, a dst that leaves ow x oh. */
+int compeg_region_tensor_shape(const compeg_tensor_spec *spec, const compeg_resize_spec *resize, uint32_t width,
+                               uint32_t height, const compeg_region *region, uint32_t *pre_width,
+                               uint32_t *pre_height, size_t *bytes_per_slot);
+/* Like compeg_*_pack_tensor_resized in everything they say about hip_stream, ordering, timing events, the decoder's
+ * texture and compeg_batch_wait.  regions (count of them) and pad are copied before the call returns.
+ * COMPEG_E_INVALID_ARG, a message about a region naming its index ("region 3: ..."), for what
+ * compeg_region_tensor_shape rejects and for: regions NULL or count 0, an image index beyond the batch (or not 0 on
+ * a decoder), a pad value that is not finite, dst_bytes smaller than the tensor, device_dst not aligned to its element
+ * size, a launch whose grid does not fit (2^31 workgroups of 256 lanes), nothing decoded yet. */
+int compeg_decoder_pack_tensor_regions(compeg_decoder *dec, const compeg_tensor_spec *spec,
+                                       const compeg_resize_spec *resize, const compeg_region *regions, size_t count,
+                                       const float *pad, void *device_dst, size_t dst_bytes, void *hip_stream);
+int compeg_batch_pack_tensor_regions(compeg_batch *batch, const compeg_tensor_spec *spec,
+                                     const compeg_resize_spec *resize, const compeg_region *regions, size_t count,
+                                     const float *pad, void *device_dst, size_t dst_bytes, void *hip_stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -49,6 +49,21 @@ pub struct compeg_rect {
     pub height: u32,
 }
 
+/// C's `float` under its own name: the signatures below read like the header's, parameter by parameter.
+#[allow(non_camel_case_types)]
+pub type float = c_float;
+
+/// One output slot of `compeg_*_pack_tensor_regions` (compeg_hip.h, "Region tensor output"): which crop of which
+/// image fills which rectangle of the slot.  An all-zero `src` is the whole image, an all-zero `dst` the whole output.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct compeg_region {
+    pub image: u32,
+    pub reserved: u32,
+    pub src: compeg_rect,
+    pub dst: compeg_rect,
+}
+
 pub const COMPEG_OK: c_int = 0;
 pub const COMPEG_E_INVALID_ARG: c_int = -1;
 pub const COMPEG_E_UNSUPPORTED: c_int = -2;
@@ -76,6 +91,8 @@ pub const COMPEG_RESIZE_NEAREST: u32 = 0;
 pub const COMPEG_RESIZE_BILINEAR: u32 = 1;
 /// A flag OR-ed into `compeg_resize_spec::filter`; only with `COMPEG_RESIZE_BILINEAR`.
 pub const COMPEG_RESIZE_ANTIALIAS: u32 = 0x100;
+pub const COMPEG_FIT_CENTER: c_uint = 0;
+pub const COMPEG_FIT_TOP_LEFT: c_uint = 1;
 
 extern "C" {
     pub fn compeg_last_error() -> *const c_char;
@@ -187,4 +204,19 @@ extern "C" {
     pub fn compeg_batch_pack_tensor_resized(batch: *mut compeg_batch, spec: *const compeg_tensor_spec,
                                             resize: *const compeg_resize_spec, crops: *const compeg_rect, device_dst: *mut c_void,
                                             dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+
+    // Region tensor output (extension)
+    pub fn compeg_region_fit(src_width: u32, src_height: u32, out_width: u32, out_height: u32, align: c_uint,
+                             dst: *mut compeg_rect) -> c_int;
+    pub fn compeg_region_tensor_shape(spec: *const compeg_tensor_spec, resize: *const compeg_resize_spec, width: u32, height: u32,
+                                      region: *const compeg_region, pre_width: *mut u32, pre_height: *mut u32,
+                                      bytes_per_slot: *mut usize) -> c_int;
+    pub fn compeg_decoder_pack_tensor_regions(dec: *mut compeg_decoder, spec: *const compeg_tensor_spec,
+                                              resize: *const compeg_resize_spec, regions: *const compeg_region, count: usize,
+                                              pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
+                                              hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_batch_pack_tensor_regions(batch: *mut compeg_batch, spec: *const compeg_tensor_spec,
+                                            resize: *const compeg_resize_spec, regions: *const compeg_region, count: usize,
+                                            pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
+                                            hip_stream: *mut c_void) -> c_int;
 }

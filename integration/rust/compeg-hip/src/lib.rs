@@ -170,6 +170,53 @@ impl ResizeSpec {
     }
 }
 
+/// One output slot of `Decoder::pack_tensor_regions` / `Batch::pack_tensor_regions` (extension; compeg_hip.h, "Region
+/// tensor output"): crop `src` of image `image` is resized into rectangle `dst` of the slot, the rest of the slot is the
+/// pad value.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct Region {
+    /// Index into the batch's last upload; 0 for a decoder.
+    pub image: u32,
+    /// `None`: the whole image.
+    pub src: Option<Rect>,
+    /// `None`: the whole output.
+    pub dst: Option<Rect>,
+}
+
+/// Where `Region::fit` puts the fitted rectangle (`COMPEG_FIT_*`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum FitAlign {
+    Center = 0,
+    TopLeft = 1,
+}
+
+impl Region {
+    pub fn whole(image: u32) -> Self {
+        Region { image, src: None, dst: None }
+    }
+
+    /// The rectangle of an `out` = (width, height) output that a crop of `src` = (width, height) pixels fills when it
+    /// is fitted with its aspect ratio kept (the letterbox's inner rectangle); no device needed.
+    pub fn fit(src: (u32, u32), out: (u32, u32), align: FitAlign) -> Result<Rect> {
+        let mut r = Rect { x: 0, y: 0, width: 0, height: 0 };
+        check(unsafe { ffi::compeg_region_fit(src.0, src.1, out.0, out.1, align as std::os::raw::c_uint, &mut r) })?;
+        Ok(r)
+    }
+
+    fn raw(&self) -> ffi::compeg_region {
+        let zero = Rect { x: 0, y: 0, width: 0, height: 0 };
+        ffi::compeg_region { image: self.image, reserved: 0, src: self.src.unwrap_or(zero), dst: self.dst.unwrap_or(zero) }
+    }
+
+    /// `(pre_width, pre_height, bytes)`: the extent of the block-averaged crop that the filter reads, and one slot in
+    /// bytes, for this region of a `width` x `height` image; checked as the pack calls check it, all but `image`.
+    pub fn shape(&self, tensor: &TensorSpec, resize: &ResizeSpec, width: u32, height: u32) -> Result<(u32, u32, usize)> {
+        let (mut w, mut h, mut n) = (0, 0, 0);
+        check(unsafe { ffi::compeg_region_tensor_shape(&tensor.raw(), &resize.raw(), width, height, &self.raw(), &mut w, &mut h, &mut n) })?;
+        Ok((w, h, n))
+    }
+}
+
 /// Device + stream + loaded gfx950 code object.  Immutable after creation and
 /// reference-counted inside the library; share it as `Arc<Gpu>` like the reference.
 pub struct Gpu {
@@ -423,6 +470,20 @@ impl Decoder {
         check(ffi::compeg_decoder_pack_tensor_resized(self.raw.as_ptr(), &spec.raw(), &resize.raw(), crop, device_dst, dst_bytes, stream.0))
     }
 
+    /// Extension: like `pack_tensor_resized`, for a list of regions of the last decoded image (`Region::image` 0), giving
+    /// `[regions.len(), 3, resize.height, resize.width]` at `device_dst`.  `pad`: R, G, B on the pixel scale (`None`:
+    /// zeros), put through the spec's scale and bias like every other element.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn pack_tensor_regions(&mut self, spec: &TensorSpec, resize: &ResizeSpec, regions: &[Region], pad: Option<&[f32; 3]>,
+                                      device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        let raw: Vec<ffi::compeg_region> = regions.iter().map(Region::raw).collect();
+        let pad = pad.map_or(ptr::null(), |p| p.as_ptr());
+        check(ffi::compeg_decoder_pack_tensor_regions(self.raw.as_ptr(), &spec.raw(), &resize.raw(), raw.as_ptr(), raw.len(), pad, device_dst,
+                                                      dst_bytes, stream.0))
+    }
+
     /// Test helper (the reference's tests copy the texture to a buffer): waits and
     /// returns the image's `width x height` corner, tightly packed.
     pub fn read_output(&mut self, width: u32, height: u32) -> Result<Vec<u8>> {
@@ -596,6 +657,20 @@ impl Batch {
         }
         let crops = crops.map_or(ptr::null(), |c| c.as_ptr());
         check(ffi::compeg_batch_pack_tensor_resized(self.raw.as_ptr(), &spec.raw(), &resize.raw(), crops, device_dst, dst_bytes, stream.0))
+    }
+
+    /// Records on `stream` the region pack of the last decode: `regions` over its images, any of them any number of
+    /// times and in any order, into `[regions.len(), 3, resize.height, resize.width]` at `device_dst`; `pad` as
+    /// `Decoder::pack_tensor_regions` has it.  `wait` covers it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn pack_tensor_regions(&mut self, spec: &TensorSpec, resize: &ResizeSpec, regions: &[Region], pad: Option<&[f32; 3]>,
+                                      device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        let raw: Vec<ffi::compeg_region> = regions.iter().map(Region::raw).collect();
+        let pad = pad.map_or(ptr::null(), |p| p.as_ptr());
+        check(ffi::compeg_batch_pack_tensor_regions(self.raw.as_ptr(), &spec.raw(), &resize.raw(), raw.as_ptr(), raw.len(), pad, device_dst,
+                                                    dst_bytes, stream.0))
     }
 
     pub fn wait(&mut self) -> Result<()> {

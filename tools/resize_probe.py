@@ -17,6 +17,11 @@ The antialias arm (--antialias; default table profiles/tensor_resize_antialias.t
 of 3840x2160 -> 224x224 in f16, at k = 1 and at the largest k that leaves both axes shrinking.  Per configuration,
 launch by launch in turn and by HIP events on one stream: the antialiased pack, the plain bilinear pack at the same
 shapes, and the decode of the same batch, which is what the pack follows in a pipeline.
+
+The regions arm (--regions; default table profiles/tensor_regions.txt), the same method: Batch.pack_tensor_regions with
+dst the whole output beside pack_tensor_resized of the same launch (the work is identical); the letterbox of 4K into
+640x640 beside the chain it replaces, a resized pack to 640x360 into a temporary and torch.nn.functional.pad; and 1024
+crops of 128x128 out of 16 4K frames in one call beside 1024 single Decoder.pack_tensor_resized calls.
 """
 import argparse
 import os
@@ -101,6 +106,159 @@ def antialias_arm(args, torch, compeg_amd, images_of, resident, gpu, stream):
     return "\n".join(lines) + "\n"
 
 
+# the regions arm, dst whole: (name, (width, height), output size, antialias)
+REGION_WHOLE_CONFIGS = (("1080p -> 224x224 bilinear", (1920, 1080), (224, 224), False),
+                        ("1080p -> 224x224 antialias", (1920, 1080), (224, 224), True),
+                        ("4K -> 224x224 bilinear", (3840, 2160), (224, 224), False),
+                        ("4K -> 224x224 antialias", (3840, 2160), (224, 224), True))
+GREY = (114.0, 114.0, 114.0)
+
+
+def _timed_in_turn(torch, stream, reps, prime, arms):
+    """Every arm launched in turn, `reps` times, between HIP events on `stream`: a list of `reps` times (ms) per arm.  The
+    order of the arms turns round from one repetition to the next, so that no arm is always the one behind another; and
+    one untimed round stands between the priming and the first timed one, whose first launch is 0.1 to 0.3 ms slower
+    whichever arm it is."""
+    with torch.cuda.stream(stream):
+        for _ in range(2):   # warm-up: code objects, the staging blocks, the allocator's blocks
+            for arm in arms:
+                arm()
+        stream.synchronize()
+        prime()
+        for arm in arms:
+            arm()
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(2 * len(arms))] for _ in range(reps)]
+        for r, e in enumerate(ev):
+            for i in range(len(arms)):
+                a = (i + r) % len(arms)
+                e[2 * a].record(stream)
+                arms[a]()
+                e[2 * a + 1].record(stream)
+        stream.synchronize()
+    return [[e[2 * a].elapsed_time(e[2 * a + 1]) for e in ev] for a in range(len(arms))]
+
+
+def _cell(x):
+    return f"{statistics.median(x):9.3f} ({min(x):.3f} .. {max(x):.3f})"
+
+
+def _gap(a, b):
+    """Whether the medians of two rows lie further apart than the rows' own min-to-max spread."""
+    return abs(statistics.median(a) - statistics.median(b)) > max(max(a) - min(a), max(b) - min(b))
+
+
+def regions_arm(args, torch, F, compeg_amd, images_of, resident, gpu, stream):
+    """The table of the regions arm, as text."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import region_reference as gr   # the header's contract in numpy
+    n, handle = args.batch, stream.cuda_stream
+    scale = [1.0 / (255.0 * s) for s in STD]
+    bias = [-m / s for m, s in zip(MEAN, STD)]
+
+    def primer(batch):
+        def prime():
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < PRIME_SECONDS:
+                batch.decode(handle)
+                batch.wait()
+        return prime
+
+    lines = [f"region tensor output: resident 4:2:2 DRI=4 frames, decoded once; {gpu.name()}",
+             f"HIP events on one stream, the arms of a row launch by launch in turn, their order turning round from one repetition to the next, one "
+             f"untimed round in front; median of {args.reps} (min .. max); f16, k = 1",
+             "",
+             f"dst whole: {n} frames, regions = Batch.pack_tensor_regions with every dst the whole output, resized = Batch.pack_tensor_resized",
+             f"{'configuration':<28} {'regions ms':>26} {'resized ms':>26} {'regions/resized':>15}"]
+    gaps = []
+    for name, (w, h), (ow, oh), antialias in REGION_WHOLE_CONFIGS:
+        items = images_of(w, h)
+        batch = resident([items[i % len(items)] for i in range(n)])
+        a = torch.empty((n, 3, oh, ow), dtype=torch.float16, device="cuda")
+        b = torch.empty((n, 3, oh, ow), dtype=torch.float16, device="cuda")
+        whole = [(i, None, None) for i in range(n)]
+        kw = dict(dtype="f16", scale=scale, bias=bias, hip_stream=handle, antialias=antialias)
+        t = _timed_in_turn(torch, stream, args.reps, primer(batch),
+                           [lambda: batch.pack_tensor_regions(a, (ow, oh), whole, pad=GREY, **kw), lambda: batch.pack_tensor_resized(b, (ow, oh), **kw)])
+        filt = "antialias" if antialias else "bilinear"
+        wrong = int((gr.expected(batch.read_output(0), (ow, oh), 1, "f16", scale, bias, "rgb", filt) != a[0].cpu().numpy()).sum())
+        equal = bool(torch.equal(a.view(torch.int16), b.view(torch.int16)))
+        lines.append(f"{name:<28} {_cell(t[0])} {_cell(t[1])} {statistics.median(t[0]) / statistics.median(t[1]):15.3f}   slot 0: {wrong} elements off the "
+                     f"contract; all slots equal to resized: {equal}")
+        print(lines[-1], file=sys.stderr, flush=True)   # (progress: the table itself is printed at the end)
+        if _gap(t[0], t[1]):
+            gaps.append(name)
+        del a, b, batch
+        torch.cuda.empty_cache()
+    lines.append("rows whose medians lie further apart than their own min-to-max spread: " + ("; ".join(gaps) if gaps else "none"))
+
+    # the letterbox: 4K fitted into 640x640; a uniform scale, so that the chain's one pad value is the contract's
+    (w, h), (ow, oh) = (3840, 2160), (640, 640)
+    dx, dy, dw, dh = compeg_amd.region_fit((w, h), (ow, oh))
+    items = images_of(w, h)
+    batch = resident([items[i % len(items)] for i in range(n)])
+    uniform, zero = [1.0 / 255.0] * 3, [0.0] * 3
+    lines += ["", f"letterbox: {n} 4K frames -> 640x640, inner rectangle ({dx}, {dy}, {dw}, {dh}), pad 114, scale 1/255; chain = pack_tensor_resized to "
+              f"{dw}x{dh} into a temporary, then torch.nn.functional.pad",
+              f"{'configuration':<28} {'regions ms':>26} {'chain ms':>26} {'chain/regions':>15}"]
+    for antialias in (False, True):
+        a = torch.empty((n, 3, oh, ow), dtype=torch.float16, device="cuda")
+        tmp = torch.empty((n, 3, dh, dw), dtype=torch.float16, device="cuda")
+        box = [(i, None, (dx, dy, dw, dh)) for i in range(n)]
+        kw = dict(dtype="f16", scale=uniform, bias=zero, hip_stream=handle, antialias=antialias)
+        kept = {}
+
+        def chain():
+            batch.pack_tensor_resized(tmp, (dw, dh), **kw)
+            kept["b"] = F.pad(tmp, (dx, ow - dx - dw, dy, oh - dy - dh), value=114.0 / 255.0)
+
+        t = _timed_in_turn(torch, stream, args.reps, primer(batch), [lambda: batch.pack_tensor_regions(a, (ow, oh), box, pad=GREY, **kw), chain])
+        filt = "antialias" if antialias else "bilinear"
+        wrong = int((gr.expected(batch.read_output(0), (ow, oh), 1, "f16", uniform, zero, "rgb", filt, None, (dx, dy, dw, dh), GREY) != a[0].cpu().numpy()).sum())
+        worst = float((a.float() - kept["b"].float()).abs().max())
+        lines.append(f"{'4K -> 640x640 ' + filt:<28} {_cell(t[0])} {_cell(t[1])} {statistics.median(t[1]) / statistics.median(t[0]):15.2f}   slot 0: {wrong} "
+                     f"elements off the contract; max |regions - chain| {worst:.4g}")
+        print(lines[-1], file=sys.stderr, flush=True)
+        del a, tmp, kept
+        torch.cuda.empty_cache()
+    del batch
+    torch.cuda.empty_cache()
+
+    # the crop list: 1024 crops of 128x128 out of 16 4K frames, one call against one call per crop
+    frames, crops, (cw, ch), (ow, oh) = 16, 1024, (128, 128), (224, 224)
+    items = [images_of(w, h)[i % len(images_of(w, h))] for i in range(frames)]
+    batch = resident(items)
+    decoders = []
+    for item in items:
+        dec = compeg_amd.Decoder(gpu)
+        dec.decode_blocking(item)
+        decoders.append(dec)
+    # (a fixed scatter: crop c comes from frame c % 16, its origin steps through the frame)
+    rects = [((c * 397) % (w - cw), (c * 211) % (h - ch), cw, ch) for c in range(crops)]
+    regions = [(c % frames, rects[c], None) for c in range(crops)]
+    lines += ["", f"crop list: {crops} crops of {cw}x{ch} out of {frames} 4K frames -> 224x224; regions = one Batch.pack_tensor_regions, singles = {crops} "
+              f"Decoder.pack_tensor_resized calls on {frames} decoders that hold the same frames",
+              f"{'configuration':<28} {'regions ms':>26} {'singles ms':>26} {'singles/regions':>15}"]
+    for antialias in (False, True):
+        a = torch.empty((crops, 3, oh, ow), dtype=torch.float16, device="cuda")
+        b = torch.empty((crops, 3, oh, ow), dtype=torch.float16, device="cuda")
+        kw = dict(dtype="f16", scale=scale, bias=bias, hip_stream=handle, antialias=antialias)
+
+        def singles():
+            for c in range(crops):
+                decoders[c % frames].pack_tensor_resized(b[c], (ow, oh), crop=rects[c], **kw)
+
+        t = _timed_in_turn(torch, stream, args.reps, primer(batch), [lambda: batch.pack_tensor_regions(a, (ow, oh), regions, pad=GREY, **kw), singles])
+        filt = "antialias" if antialias else "bilinear"
+        wrong = int((gr.expected(batch.read_output(0), (ow, oh), 1, "f16", scale, bias, "rgb", filt, rects[0]) != a[0].cpu().numpy()).sum())
+        equal = bool(torch.equal(a.view(torch.int16), b.view(torch.int16)))
+        lines.append(f"{'128x128 -> 224x224 ' + filt:<28} {_cell(t[0])} {_cell(t[1])} {statistics.median(t[1]) / statistics.median(t[0]):15.2f}   slot 0: {wrong} "
+                     f"elements off the contract; all slots equal to the singles: {equal}")
+        print(lines[-1], file=sys.stderr, flush=True)
+        del a, b
+        torch.cuda.empty_cache()
+    return "\n".join(lines) + "\n"
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=256)
@@ -109,9 +267,11 @@ def main():
     p.add_argument("--threads", type=int, default=16)
     p.add_argument("--out", default=None, help="default: profiles/tensor_resize.txt, or profiles/tensor_resize_antialias.txt with --antialias")
     p.add_argument("--antialias", action="store_true", help="the antialias arm instead of the table against the chain")
+    p.add_argument("--regions", action="store_true", help="the regions arm (Batch.pack_tensor_regions) instead; default table profiles/tensor_regions.txt")
     args = p.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "tensor_resize_antialias.txt" if args.antialias else "tensor_resize.txt")
+        args.out = os.path.join(ROOT, "profiles", "tensor_regions.txt" if args.regions else
+                                "tensor_resize_antialias.txt" if args.antialias else "tensor_resize.txt")
 
     import torch
     import torch.nn.functional as F
@@ -143,8 +303,9 @@ def main():
         batch.wait()
         return batch
 
-    if args.antialias:
-        text = antialias_arm(args, torch, compeg_amd, images_of, resident, gpu, stream)
+    if args.antialias or args.regions:
+        text = (regions_arm(args, torch, F, compeg_amd, images_of, resident, gpu, stream) if args.regions else
+                antialias_arm(args, torch, compeg_amd, images_of, resident, gpu, stream))
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             f.write(text)
