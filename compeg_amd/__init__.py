@@ -18,12 +18,12 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
-                   LIB_PATH, METADATA_BYTES, Error, Rect, Region, ResizeSpec, TensorSpec, check, lib)
+                   LIB_PATH, METADATA_BYTES, Error, FilterSpec, Rect, Region, ResizeSpec, TensorSpec, check, lib)
 
 __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Texture", "Error", "HostBuffer", "JpegList",
            "host_register", "host_unregister", "version", "LIB_PATH", "tensor_shape", "TENSOR_DTYPES", "TENSOR_ORDERS",
            "resized_tensor_shape", "RESIZE_FILTERS", "ResizeSpec", "Rect", "Region", "FIT_ALIGNS", "region_fit",
-           "region_tensor_shape"]
+           "region_tensor_shape", "FILTER_KERNELS", "FilterSpec", "filtered_tensor_shape"]
 
 
 # compeg_decoder_last_kernel / compeg_batch_last_kernel (include/compeg_hip.h: COMPEG_KERNEL_*)
@@ -147,6 +147,33 @@ def region_tensor_shape(width, height, size, region=None, dtype="f16", downscale
     check(lib.compeg_region_tensor_shape(C.byref(spec), C.byref(resize), width, height, C.byref(r) if r is not None else None,
                                          C.byref(pw), C.byref(ph), C.byref(nbytes)))
     return (3, resize.out_height, resize.out_width), nbytes.value, (ph.value, pw.value)
+
+
+# Filtered tensor output (include/compeg_hip.h: COMPEG_FILTER_*): resampling kernels by name
+FILTER_KERNELS = {"box": 0, "triangle": 1, "bicubic": 2, "lanczos3": 3}
+
+
+def _filter_spec(size, kernel):
+    """compeg_filter_spec from size = (ow, oh) and a kernel's name (or the header's number, which the library checks)."""
+    if isinstance(kernel, str) and kernel not in FILTER_KERNELS:
+        raise Error(f"unknown filter kernel {kernel!r} (one of {', '.join(FILTER_KERNELS)})")
+    spec = FilterSpec()
+    spec.out_width, spec.out_height = size
+    spec.kernel, spec.reserved = FILTER_KERNELS[kernel] if isinstance(kernel, str) else kernel, 0
+    return spec
+
+
+def filtered_tensor_shape(width, height, size, region=None, kernel="bicubic", dtype="f16", downscale=1):
+    """((3, oh, ow), bytes, (ph, pw)) of one slot of a filtered pack: region_tensor_shape for pack_tensor_filtered, the
+    kernel's tap limit (box reduces by 128 at the most, triangle 64, bicubic 32, lanczos3 21) taken against dst's extent
+    (compeg_filtered_tensor_shape; no device needed)."""
+    spec = _tensor_spec(dtype, downscale, (1, 1, 1), (0, 0, 0), "rgb")
+    filter = _filter_spec(size, kernel)
+    r = _region(region) if region is not None else None
+    pw, ph, nbytes = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    check(lib.compeg_filtered_tensor_shape(C.byref(spec), C.byref(filter), width, height, C.byref(r) if r is not None else None,
+                                           C.byref(pw), C.byref(ph), C.byref(nbytes)))
+    return (3, filter.out_height, filter.out_width), nbytes.value, (ph.value, pw.value)
 
 
 def _device_range(dst):
@@ -506,6 +533,18 @@ class Decoder:
         check(lib.compeg_decoder_pack_tensor_regions(self._h, C.byref(spec), C.byref(resize), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
                                                      C.c_void_p(hip_stream)))
 
+    def pack_tensor_filtered(self, dst, size, regions=None, kernel="bicubic", pad=(0, 0, 0), dtype="f16", downscale=1, scale=(1, 1, 1),
+                             bias=(0, 0, 0), order="rgb", hip_stream=0):
+        """Extension (compeg_decoder_pack_tensor_filtered): pack_tensor_regions with one of FILTER_KERNELS -- PIL's box,
+        triangle (BILINEAR), bicubic and lanczos3 resampling, each widened with the reduction.  regions=None: the whole
+        image into the whole output, [1, 3, oh, ow].  Returns without waiting, like pack_tensor."""
+        spec = _tensor_spec(dtype, downscale, scale, bias, order)
+        filter = _filter_spec(size, kernel)
+        list_, n = _regions(regions if regions is not None else [(0, None, None)])
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_decoder_pack_tensor_filtered(self._h, C.byref(spec), C.byref(filter), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
+                                                      C.c_void_p(hip_stream)))
+
     def read_coefficients(self, total_dus):
         out = np.empty(total_dus * 32, dtype=np.int32)
         check(lib.compeg_decoder_read_coefficients(self._h, out.ctypes.data, out.size))
@@ -623,6 +662,18 @@ class Batch:
         addr, nbytes = _device_range(dst)
         check(lib.compeg_batch_pack_tensor_regions(self._h, C.byref(spec), C.byref(resize), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
                                                    C.c_void_p(hip_stream)))
+
+    def pack_tensor_filtered(self, dst, size, regions=None, kernel="bicubic", pad=(0, 0, 0), dtype="f16", downscale=1, scale=(1, 1, 1),
+                             bias=(0, 0, 0), order="rgb", hip_stream=0):
+        """Extension (compeg_batch_pack_tensor_filtered): Decoder.pack_tensor_filtered over the last decode's images, regions as
+        pack_tensor_regions takes them.  regions=None: every image, whole, into the whole output of its own slot,
+        [count, 3, oh, ow].  Returns without waiting; wait() covers it."""
+        spec = _tensor_spec(dtype, downscale, scale, bias, order)
+        filter = _filter_spec(size, kernel)
+        list_, n = _regions(regions if regions is not None else [(i, None, None) for i in range(self.count())])
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_batch_pack_tensor_filtered(self._h, C.byref(spec), C.byref(filter), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
+                                                    C.c_void_p(hip_stream)))
 
     def algorithmic_bytes(self):
         return lib.compeg_batch_algorithmic_bytes(self._h)

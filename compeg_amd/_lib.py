@@ -44,6 +44,11 @@ class Region(C.Structure):
     _fields_ = [("image", C.c_uint32), ("reserved", C.c_uint32), ("src", Rect), ("dst", Rect)]
 
 
+class FilterSpec(C.Structure):
+    """compeg_filter_spec (include/compeg_hip.h, "Filtered tensor output")."""
+    _fields_ = [("out_width", C.c_uint32), ("out_height", C.c_uint32), ("kernel", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -130,6 +135,9 @@ def _load():
         "compeg_region_tensor_shape": (i, [C.POINTER(TensorSpec), C.POINTER(ResizeSpec), u32, u32, C.POINTER(Region), pu32, pu32, psz]),
         "compeg_decoder_pack_tensor_regions": (i, [vp, C.POINTER(TensorSpec), C.POINTER(ResizeSpec), C.POINTER(Region), sz, C.POINTER(C.c_float), vp, sz, vp]),
         "compeg_batch_pack_tensor_regions": (i, [vp, C.POINTER(TensorSpec), C.POINTER(ResizeSpec), C.POINTER(Region), sz, C.POINTER(C.c_float), vp, sz, vp]),
+        "compeg_filtered_tensor_shape": (i, [C.POINTER(TensorSpec), C.POINTER(FilterSpec), u32, u32, C.POINTER(Region), pu32, pu32, psz]),
+        "compeg_decoder_pack_tensor_filtered": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(Region), sz, C.POINTER(C.c_float), vp, sz, vp]),
+        "compeg_batch_pack_tensor_filtered": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(Region), sz, C.POINTER(C.c_float), vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("COMPEG_LIB") and not hasattr(L, name):

@@ -275,6 +275,61 @@ bool region_tensor_bytes(const compeg_resize_spec *resize, size_t elem, size_t c
     return true;
 }
 
+// compeg_filter_spec as the header has it.  (The texts name values, not the header's macros.)
+int check_filter_spec(const compeg_filter_spec *filter)
+{
+    if (!filter)
+        return fail(COMPEG_E_INVALID_ARG, "filter is NULL");
+    if (filter->out_width == 0u || filter->out_height == 0u || filter->out_width > 65535u || filter->out_height > 65535u)
+        return fail(COMPEG_E_INVALID_ARG, ("filter: output size " + std::to_string(filter->out_width) + "x" + std::to_string(filter->out_height) +
+                                           " is not within 1..65535 both ways").c_str());
+    if (filter->kernel > COMPEG_FILTER_LANCZOS3)
+        return fail(COMPEG_E_INVALID_ARG, ("filter: kernel " + std::to_string(filter->kernel) +
+                                           " is none of 0 (box), 1 (triangle), 2 (bicubic), 3 (lanczos3)").c_str());
+    if (filter->reserved != 0u)
+        return fail(COMPEG_E_INVALID_ARG, "filter: reserved must be 0");
+    return COMPEG_OK;
+}
+
+// One region of a filtered call: check_region with the kernel's tap limit, n * 2S <= 128 * o both ways against the
+// inner extent, in place of the antialias flag's.
+int check_filtered_region(const compeg_region *region, const compeg_tensor_spec *spec, const compeg_filter_spec *filter, uint32_t width,
+                          uint32_t height, const std::string &which, compeg_region *out)
+{
+    const compeg_resize_spec extent{filter->out_width, filter->out_height, COMPEG_RESIZE_BILINEAR, 0u}; // (no flag: no ratio check there)
+    const int rc = check_region(region, spec, &extent, width, height, which, out);
+    if (rc != COMPEG_OK)
+        return rc;
+    static const char *const names[] = {"box", "triangle", "bicubic", "lanczos3"};
+    static const uint32_t twice_support[] = {1u, 2u, 4u, 6u}, most[] = {128u, 64u, 32u, 21u};
+    const uint32_t pw = out->src.width / spec->downscale, ph = out->src.height / spec->downscale, s2 = twice_support[filter->kernel];
+    if (uint64_t(pw) * s2 > 128u * uint64_t(out->dst.width) || uint64_t(ph) * s2 > 128u * uint64_t(out->dst.height))
+        return fail(COMPEG_E_INVALID_ARG, ("filter: " + which + names[filter->kernel] + " reduces by " + std::to_string(most[filter->kernel]) +
+                                           " at the most either way, " + std::to_string(pw) + "x" + std::to_string(ph) + " to " +
+                                           std::to_string(out->dst.width) + "x" + std::to_string(out->dst.height) + " is more: choose a larger downscale")
+                                              .c_str());
+    return COMPEG_OK;
+}
+
+// What both filtered packs check before they look at their object: the specs, the list, the pad.
+int check_filtered_call(const compeg_tensor_spec *spec, const compeg_filter_spec *filter, const compeg_region *regions, size_t count,
+                        const float *pad, size_t *elem_bytes)
+{
+    int rc = check_tensor_spec(spec, elem_bytes);
+    if (rc == COMPEG_OK)
+        rc = check_filter_spec(filter);
+    if (rc != COMPEG_OK)
+        return rc;
+    if (!regions)
+        return fail(COMPEG_E_INVALID_ARG, "tensor: regions is NULL");
+    if (count == 0)
+        return fail(COMPEG_E_INVALID_ARG, "tensor: a region count of 0");
+    for (int c = 0; pad && c < 3; c++)
+        if (!std::isfinite(pad[c]))
+            return fail(COMPEG_E_INVALID_ARG, ("tensor: pad of channel " + std::to_string(c) + " is not finite").c_str());
+    return COMPEG_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1390,6 +1445,112 @@ int compeg_batch_pack_tensor_regions(compeg_batch *batch, const compeg_tensor_sp
         const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
         Status s = batch->pack_tensor_regions(*spec, *resize, list.data(), count, pad_copy, device_dst,
                                               hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream);
+        return s.ok() ? ok() : fail(s);
+    });
+}
+
+/* ---- Filtered tensor output ------------------------------------------------ */
+
+int compeg_filtered_tensor_shape(const compeg_tensor_spec *spec, const compeg_filter_spec *filter, uint32_t width, uint32_t height,
+                                 const compeg_region *region, uint32_t *pre_width, uint32_t *pre_height, size_t *bytes_per_slot)
+{
+    return guarded([&] {
+        size_t elem = 0;
+        int rc = check_tensor_spec(spec, &elem);
+        if (rc == COMPEG_OK)
+            rc = check_filter_spec(filter);
+        compeg_region r{};
+        if (rc == COMPEG_OK)
+            rc = check_filtered_region(region, spec, filter, width, height, "", &r);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (pre_width)
+            *pre_width = r.src.width / spec->downscale;
+        if (pre_height)
+            *pre_height = r.src.height / spec->downscale;
+        if (bytes_per_slot)
+            *bytes_per_slot = size_t(3) * size_t(filter->out_height) * size_t(filter->out_width) * elem;
+        return ok();
+    });
+}
+
+int compeg_decoder_pack_tensor_filtered(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
+                                        const compeg_region *regions, size_t count, const float *pad, void *device_dst, size_t dst_bytes,
+                                        void *hip_stream)
+{
+    return guarded([&] {
+        // (what does not depend on the object first: it is checked where no device is)
+        size_t elem = 0, bytes = 0;
+        int rc = check_filtered_call(spec, filter, regions, count, pad, &elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (!dec)
+            return fail(COMPEG_E_INVALID_ARG, "dec is NULL");
+        if (!dec->have_last || !dec->out.ptr)
+            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
+        const compeg_resize_spec extent{filter->out_width, filter->out_height, COMPEG_RESIZE_BILINEAR, 0u};
+        if (!region_tensor_bytes(&extent, elem, count, &bytes))
+            return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
+        // (the launch's limits and the destination before the list is copied: nothing is allocated for a count no call takes)
+        if (count > 0xffffffffull || !compeg::filter_grid_fits(uint32_t(count), *spec, *filter))
+            return fail(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
+        rc = check_tensor_destination(device_dst, dst_bytes, bytes, elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        // (the copy of the caller's list: src and dst as whole rectangles)
+        std::vector<compeg_region> list(count);
+        for (size_t r = 0; r < count; r++) {
+            const std::string which = "region " + std::to_string(r) + ": ";
+            if (regions[r].image != 0u)
+                return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "image " + std::to_string(regions[r].image) + ", a decoder has image 0 only").c_str());
+            rc = check_filtered_region(regions + r, spec, filter, dec->last_w, dec->last_h, which, &list[r]);
+            if (rc != COMPEG_OK)
+                return rc;
+        }
+        const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
+        Status s = dec->pack_tensor_filtered(*spec, *filter, list.data(), count, pad_copy, device_dst,
+                                             hip_stream ? static_cast<hipStream_t>(hip_stream) : dec->gpu->stream);
+        return s.ok() ? ok() : fail(s);
+    });
+}
+
+int compeg_batch_pack_tensor_filtered(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
+                                      const compeg_region *regions, size_t count, const float *pad, void *device_dst, size_t dst_bytes,
+                                      void *hip_stream)
+{
+    return guarded([&] {
+        // (what does not depend on the object first: it is checked where no device is)
+        size_t elem = 0, bytes = 0;
+        int rc = check_filtered_call(spec, filter, regions, count, pad, &elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (!batch)
+            return fail(COMPEG_E_INVALID_ARG, "batch is NULL");
+        if (!batch->count || !batch->output_decoded)
+            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
+        const compeg_resize_spec extent{filter->out_width, filter->out_height, COMPEG_RESIZE_BILINEAR, 0u};
+        if (!region_tensor_bytes(&extent, elem, count, &bytes))
+            return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
+        // (the launch's limits and the destination before the list is copied: nothing is allocated for a count no call takes)
+        if (count > 0xffffffffull || !compeg::filter_grid_fits(uint32_t(count), *spec, *filter))
+            return fail(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
+        rc = check_tensor_destination(device_dst, dst_bytes, bytes, elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        std::vector<compeg_region> list(count);
+        for (size_t r = 0; r < count; r++) {
+            const std::string which = "region " + std::to_string(r) + ": ";
+            const uint32_t i = regions[r].image;
+            if (i >= batch->count)
+                return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "image " + std::to_string(i) + " is beyond the batch's " +
+                                                   std::to_string(batch->count) + " images").c_str());
+            rc = check_filtered_region(regions + r, spec, filter, batch->descs[i].out_w, batch->descs[i].out_h, which, &list[r]);
+            if (rc != COMPEG_OK)
+                return rc;
+        }
+        const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
+        Status s = batch->pack_tensor_filtered(*spec, *filter, list.data(), count, pad_copy, device_dst,
+                                               hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream);
         return s.ok() ? ok() : fail(s);
     });
 }

@@ -151,6 +151,22 @@ bool region_grid_fits(uint32_t slots, const compeg_tensor_spec &spec, const comp
 hipError_t launch_region_tensor(const void *device_blob, size_t tables_at, uint32_t slots, const compeg_tensor_spec &spec,
                                 const compeg_resize_spec &resize, const float *pad, void *dst, hipStream_t stream);
 
+// Filtered tensor output (filter_kernels.hip, filter_body.h): the region pack's records with the axis tables of one of
+// the four kernels (COMPEG_FILTER_*) behind them, as one blob; a lane is a column of a band of kFilterBand output rows.
+#if defined(CG_FILTER_BAND)
+constexpr uint32_t kFilterBand = CG_FILTER_BAND; // (a measurement build with another band: DESIGN.md 5.11, "Measured")
+#else
+constexpr uint32_t kFilterBand = 8;
+#endif
+// False: a crop is smaller than k or an axis is beyond the tap limit (the caller has checked both), or the call's tables
+// outgrow the 32 bits their offsets have.
+bool make_filter_blob(std::vector<uint32_t> &blob, size_t &tables_at, const RegionSource *sources, uint32_t slots, uint32_t k,
+                      uint32_t kernel);
+bool filter_grid_fits(uint32_t slots, const compeg_tensor_spec &spec, const compeg_filter_spec &filter);
+// pad: three values on the pixel scale by source channel (R, G, B), or null for zeros.
+hipError_t launch_filter_tensor(const void *device_blob, size_t tables_at, uint32_t slots, const compeg_tensor_spec &spec,
+                                const compeg_filter_spec &filter, const float *pad, void *dst, hipStream_t stream);
+
 #if defined(CG_AC_STAMPS)
 // diagnostic build: AC-loop cycle counters (kernels_body.h)
 hipError_t read_ac_stamps(unsigned long long out[4], bool reset);

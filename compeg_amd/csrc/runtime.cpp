@@ -2460,6 +2460,68 @@ Status compeg_batch::pack_tensor_regions(const compeg_tensor_spec &spec, const c
     return Status{};
 }
 
+// What a filtered pack says when its records and tables could not be made (the C layer has checked crops and taps).
+static const char kFilterNoBlob[] = "tensor: a region's crop is smaller than the downscale factor or beyond the kernel's tap limit, or this "
+                                    "call's filter tables outgrow 2^32 words";
+
+// Filtered tensor output: pack_tensor_regions' ordering and staging with the filter kernels' tables and launch.
+Status compeg_decoder::pack_tensor_filtered(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_region *regions,
+                                            size_t count, const float *pad, void *dst, hipStream_t stream)
+{
+    CG_HIP(hipSetDevice(gpu->device));
+    // (the limits first: nothing is allocated for a count that no launch takes)
+    if (count > 0xffffffffull || !filter_grid_fits(uint32_t(count), spec, filter))
+        return Status::error(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
+    std::vector<RegionSource> placements(count);
+    for (size_t r = 0; r < count; r++)
+        placements[r] = RegionSource{out.ptr, uint32_t(out_pitch), regions[r].src, regions[r].dst};
+    std::vector<uint32_t> blob;
+    size_t tables_at = 0;
+    if (!make_filter_blob(blob, tables_at, placements.data(), uint32_t(count), spec.downscale, filter.kernel))
+        return Status::error(COMPEG_E_INVALID_ARG, kFilterNoBlob);
+    if (!decode_done)
+        CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
+    if (decode_pending && stream != last_stream)
+        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
+    const void *records = nullptr;
+    CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &records));
+    CG_HIP(launch_filter_tensor(records, tables_at, uint32_t(count), spec, filter, pad, dst, stream));
+    CG_HIP(hipEventRecord(decode_done, stream));
+    decode_pending = true;
+    last_stream = stream;
+    return Status{};
+}
+
+Status compeg_batch::pack_tensor_filtered(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_region *regions,
+                                          size_t count, const float *pad, void *dst, hipStream_t stream)
+{
+    CG_HIP(hipSetDevice(gpu->device));
+    // (the limits first: nothing is allocated for a count that no launch takes)
+    if (count > 0xffffffffull || !filter_grid_fits(uint32_t(count), spec, filter))
+        return Status::error(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
+    std::vector<RegionSource> placements(count);
+    for (size_t r = 0; r < count; r++) {
+        const ImageDesc &d = descs[regions[r].image];
+        placements[r] = RegionSource{d.out, d.out_pitch, regions[r].src, regions[r].dst};
+    }
+    std::vector<uint32_t> blob;
+    size_t tables_at = 0;
+    if (!make_filter_blob(blob, tables_at, placements.data(), uint32_t(count), spec.downscale, filter.kernel))
+        return Status::error(COMPEG_E_INVALID_ARG, kFilterNoBlob);
+    if (decode_recorded && stream != last_stream) {
+        if (!decode_done)
+            CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
+        CG_HIP(hipEventRecord(decode_done, last_stream));
+        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
+    }
+    const void *device_records = nullptr;
+    CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &device_records));
+    CG_HIP(launch_filter_tensor(device_records, tables_at, uint32_t(count), spec, filter, pad, dst, stream));
+    // (no timing events; the next decode on another stream records decode_done on last_stream, behind this)
+    last_stream = stream;
+    return Status{};
+}
+
 Status compeg_batch::pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream)
 {
     CG_HIP(hipSetDevice(gpu->device));

@@ -159,6 +159,9 @@ struct compeg_decoder {
     // whole rectangles by now, and inside the image and the output (checked by the caller, like specs, pad and dst)
     compeg::Status pack_tensor_regions(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_region *regions,
                                        size_t count, const float *pad, void *dst, hipStream_t stream);
+    // Filtered tensor output: pack_tensor_regions with one of the four resampling kernels (the tap limit checked by the caller too)
+    compeg::Status pack_tensor_filtered(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_region *regions,
+                                        size_t count, const float *pad, void *dst, hipStream_t stream);
     compeg::Status check_scan_result(bool &fell_back);
     compeg::Status preprocess_on_device(const compeg::ImageData &img, hipStream_t stream, uint32_t &nwords,
                                         uint32_t &nstarts, uint32_t &span, bool &fell_back, size_t blob_bytes,
@@ -263,4 +266,7 @@ struct compeg_batch {
     // now, and inside their image and the output (checked by the caller, like specs, pad and dst)
     compeg::Status pack_tensor_regions(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_region *regions,
                                        size_t count, const float *pad, void *dst, hipStream_t stream);
+    // Filtered tensor output: pack_tensor_regions with one of the four resampling kernels (the tap limit checked by the caller too)
+    compeg::Status pack_tensor_filtered(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_region *regions,
+                                        size_t count, const float *pad, void *dst, hipStream_t stream);
 };

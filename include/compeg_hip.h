@@ -491,6 +491,61 @@ int compeg_batch_pack_tensor_regions(compeg_batch *batch, const compeg_tensor_sp
                                      const compeg_resize_spec *resize, const compeg_region *regions, size_t count,
                                      const float *pad, void *device_dst, size_t dst_bytes, void *hip_stream);
 
+/* ---- Filtered tensor output (extension) --------------------------------------
+ * compeg_*_pack_tensor_regions with the separable resampling kernels of PIL's Image.resize, each widened with the
+ * reduction: box (area averaging), triangle (PIL's BILINEAR), bicubic with a = -0.5 (PIL's BICUBIC, torch's
+ * interpolate(mode="bicubic", antialias=True)) and Lanczos of support 3.  New entry points beside the old ones: no
+ * existing call does anything different.
+ *
+ * Regions, crops, inner rectangles, pad, destination, writes: the region tensor output's, above.  The prefilter P (crop,
+ * downscale k, block mean), scale, bias, order, the conversions and the u8 clamp: the resized tensor output's.
+ * Each axis on its own: n its prefiltered extent (pw or ph), o the inner extent (dw or dh), S the kernel's support
+ * (0.5, 1, 2, 3), x the output coordinate counted inside the inner rectangle.  On the host, in double:
+ *   s = double(n) / double(o);  sc = max(s, 1.0);  sup = S * sc;  inv = 1.0 / sc;  c = s * (x + 0.5)
+ *   lo = max(int64(c - sup + 0.5), 0);  hi = min(int64(c + sup + 0.5), n)      (truncated toward zero)
+ *   first = lo;  count = hi - lo  (>= 1)
+ *   u_t = f((t + lo - c + 0.5) * inv), t = 0 .. count - 1;  total = u_0 + u_1 + ..  (ascending t);  w_t = float(u_t / total)
+ * with f(z):
+ *   box:       1 for -0.5 < z <= 0.5, else 0
+ *   triangle:  max(0, 1 - |z|)
+ *   bicubic:   a = -0.5, q = |z|:  ((a + 2) q - (a + 3)) q q + 1 for q < 1;  (((q - 5) q + 8) q - 4) a for q < 2;  else 0
+ *   lanczos3:  sinc(z) sinc(z / 3) for -3 <= z < 3, else 0;  sinc(0) = 1, sinc(z) = sin(pi z) / (pi z), sin the C library's
+ * Weights may be negative.  Tap t reads index first + t, always inside the axis: no pixel outside the crop is read.
+ * Then in f32, every operation rounded on its own, never fused:
+ *   h(j) = P[j][i_0] * wx_0;  then h = h + (P[j][i_t] * wx_t) for the further x taps          (horizontal, row j)
+ *   m = h(j_0) * wy_0;  then m = m + (h(j_t) * wy_t) over the y taps' rows in ascending order  (vertical)
+ *   v = (m * scale[c]) + bias[c], converted and stored like every other tensor element (u8: rounded to even, clamped to
+ *   0..255 -- bicubic and Lanczos overshoot at hard edges)
+ * Tap limit: a region is rejected when n * 2S > 128 * o on either axis (2S = 1, 2, 4, 6: box reduces by 128 at the
+ * most, triangle by 64, bicubic by 32, Lanczos by 21); count is then 129 at the most.  Choose a larger downscale.
+ * What follows: triangle where both axes shrink is COMPEG_RESIZE_BILINEAR | COMPEG_RESIZE_ANTIALIAS of the same
+ * regions, bit for bit; box at o = n / 2, n / 4, n / 8 (n divisible) is compeg_*_pack_tensor at that downscale; box,
+ * triangle and bicubic at o = n are compeg_*_pack_tensor of the crop (Lanczos is not: sin(k pi) is not 0 in double). */
+#define COMPEG_FILTER_BOX 0      /* support 0.5: area averaging */
+#define COMPEG_FILTER_TRIANGLE 1 /* support 1: PIL's BILINEAR */
+#define COMPEG_FILTER_BICUBIC 2  /* support 2, a = -0.5: PIL's BICUBIC, torch's bicubic with antialias=True */
+#define COMPEG_FILTER_LANCZOS3 3 /* support 3: PIL's LANCZOS */
+typedef struct compeg_filter_spec {
+    uint32_t out_width, out_height; /* 1 .. 65535 */
+    uint32_t kernel;                /* COMPEG_FILTER_* */
+    uint32_t reserved;              /* 0 */
+} compeg_filter_spec;               /* 16 bytes */
+/* No device needed: compeg_region_tensor_shape for the filtered calls.  COMPEG_E_INVALID_ARG for what that rejects of
+ * spec, the output extent and the region, and for: an unknown kernel, reserved != 0, an axis beyond the tap limit (the
+ * message names both extents and advises a larger downscale). */
+int compeg_filtered_tensor_shape(const compeg_tensor_spec *spec, const compeg_filter_spec *filter, uint32_t width,
+                                 uint32_t height, const compeg_region *region, uint32_t *pre_width,
+                                 uint32_t *pre_height, size_t *bytes_per_slot);
+/* Like compeg_*_pack_tensor_regions in everything they say about hip_stream, ordering, timing events, the decoder's
+ * texture, compeg_batch_wait, the copies made before the call returns, the messages and the rejections, with
+ * compeg_filtered_tensor_shape's in place of compeg_region_tensor_shape's. */
+int compeg_decoder_pack_tensor_filtered(compeg_decoder *dec, const compeg_tensor_spec *spec,
+                                        const compeg_filter_spec *filter, const compeg_region *regions, size_t count,
+                                        const float *pad, void *device_dst, size_t dst_bytes, void *hip_stream);
+int compeg_batch_pack_tensor_filtered(compeg_batch *batch, const compeg_tensor_spec *spec,
+                                      const compeg_filter_spec *filter, const compeg_region *regions, size_t count,
+                                      const float *pad, void *device_dst, size_t dst_bytes, void *hip_stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

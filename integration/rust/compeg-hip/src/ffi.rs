@@ -64,6 +64,17 @@ pub struct compeg_region {
     pub dst: compeg_rect,
 }
 
+/// The output extent and the resampling kernel of `compeg_*_pack_tensor_filtered` (compeg_hip.h, "Filtered tensor
+/// output").
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct compeg_filter_spec {
+    pub out_width: u32,
+    pub out_height: u32,
+    pub kernel: u32,
+    pub reserved: u32,
+}
+
 pub const COMPEG_OK: c_int = 0;
 pub const COMPEG_E_INVALID_ARG: c_int = -1;
 pub const COMPEG_E_UNSUPPORTED: c_int = -2;
@@ -93,6 +104,10 @@ pub const COMPEG_RESIZE_BILINEAR: u32 = 1;
 pub const COMPEG_RESIZE_ANTIALIAS: u32 = 0x100;
 pub const COMPEG_FIT_CENTER: c_uint = 0;
 pub const COMPEG_FIT_TOP_LEFT: c_uint = 1;
+pub const COMPEG_FILTER_BOX: u32 = 0;
+pub const COMPEG_FILTER_TRIANGLE: u32 = 1;
+pub const COMPEG_FILTER_BICUBIC: u32 = 2;
+pub const COMPEG_FILTER_LANCZOS3: u32 = 3;
 
 extern "C" {
     pub fn compeg_last_error() -> *const c_char;
@@ -219,4 +234,17 @@ extern "C" {
                                             resize: *const compeg_resize_spec, regions: *const compeg_region, count: usize,
                                             pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
                                             hip_stream: *mut c_void) -> c_int;
+
+    // Filtered tensor output (extension)
+    pub fn compeg_filtered_tensor_shape(spec: *const compeg_tensor_spec, filter: *const compeg_filter_spec, width: u32, height: u32,
+                                        region: *const compeg_region, pre_width: *mut u32, pre_height: *mut u32,
+                                        bytes_per_slot: *mut usize) -> c_int;
+    pub fn compeg_decoder_pack_tensor_filtered(dec: *mut compeg_decoder, spec: *const compeg_tensor_spec,
+                                               filter: *const compeg_filter_spec, regions: *const compeg_region, count: usize,
+                                               pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
+                                               hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_batch_pack_tensor_filtered(batch: *mut compeg_batch, spec: *const compeg_tensor_spec,
+                                             filter: *const compeg_filter_spec, regions: *const compeg_region, count: usize,
+                                             pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
+                                             hip_stream: *mut c_void) -> c_int;
 }

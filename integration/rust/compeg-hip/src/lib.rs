@@ -217,6 +217,45 @@ impl Region {
     }
 }
 
+/// Resampling kernel of a filtered pack (`COMPEG_FILTER_*`): PIL's `Image.resize` filters, each widened with the
+/// reduction.  `Triangle` is PIL's BILINEAR, `Bicubic` (a = -0.5) PIL's BICUBIC and torch's bicubic with
+/// `antialias=True`, `Lanczos3` PIL's LANCZOS.  The block-averaged crop may be 128, 64, 32 and 21 times the inner
+/// rectangle at the most either way.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum FilterKernel {
+    Box = 0,
+    Triangle = 1,
+    Bicubic = 2,
+    Lanczos3 = 3,
+}
+
+/// The fixed output extent and the kernel of `Decoder::pack_tensor_filtered` / `Batch::pack_tensor_filtered`
+/// (extension; compeg_hip.h, "Filtered tensor output").
+#[derive(Clone, Copy, Debug)]
+pub struct FilterSpec {
+    pub width: u32,
+    pub height: u32,
+    pub kernel: FilterKernel,
+}
+
+impl FilterSpec {
+    pub fn new(width: u32, height: u32, kernel: FilterKernel) -> Self {
+        FilterSpec { width, height, kernel }
+    }
+
+    fn raw(&self) -> ffi::compeg_filter_spec {
+        ffi::compeg_filter_spec { out_width: self.width, out_height: self.height, kernel: self.kernel as u32, reserved: 0 }
+    }
+
+    /// `(pre_width, pre_height, bytes)`: `Region::shape` for the filtered calls, the kernel's tap limit checked against
+    /// the region's inner rectangle; no device needed.
+    pub fn shape(&self, tensor: &TensorSpec, region: &Region, width: u32, height: u32) -> Result<(u32, u32, usize)> {
+        let (mut w, mut h, mut n) = (0, 0, 0);
+        check(unsafe { ffi::compeg_filtered_tensor_shape(&tensor.raw(), &self.raw(), width, height, &region.raw(), &mut w, &mut h, &mut n) })?;
+        Ok((w, h, n))
+    }
+}
+
 /// Device + stream + loaded gfx950 code object.  Immutable after creation and
 /// reference-counted inside the library; share it as `Arc<Gpu>` like the reference.
 pub struct Gpu {
@@ -484,6 +523,18 @@ impl Decoder {
                                                       dst_bytes, stream.0))
     }
 
+    /// Extension: `pack_tensor_regions` with one of the four resampling kernels of `FilterSpec`.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn pack_tensor_filtered(&mut self, spec: &TensorSpec, filter: &FilterSpec, regions: &[Region], pad: Option<&[f32; 3]>,
+                                       device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        let raw: Vec<ffi::compeg_region> = regions.iter().map(Region::raw).collect();
+        let pad = pad.map_or(ptr::null(), |p| p.as_ptr());
+        check(ffi::compeg_decoder_pack_tensor_filtered(self.raw.as_ptr(), &spec.raw(), &filter.raw(), raw.as_ptr(), raw.len(), pad, device_dst,
+                                                       dst_bytes, stream.0))
+    }
+
     /// Test helper (the reference's tests copy the texture to a buffer): waits and
     /// returns the image's `width x height` corner, tightly packed.
     pub fn read_output(&mut self, width: u32, height: u32) -> Result<Vec<u8>> {
@@ -671,6 +722,19 @@ impl Batch {
         let pad = pad.map_or(ptr::null(), |p| p.as_ptr());
         check(ffi::compeg_batch_pack_tensor_regions(self.raw.as_ptr(), &spec.raw(), &resize.raw(), raw.as_ptr(), raw.len(), pad, device_dst,
                                                     dst_bytes, stream.0))
+    }
+
+    /// Records on `stream` the filtered pack of the last decode: `pack_tensor_regions` with one of the four resampling
+    /// kernels of `FilterSpec`.  `wait` covers it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn pack_tensor_filtered(&mut self, spec: &TensorSpec, filter: &FilterSpec, regions: &[Region], pad: Option<&[f32; 3]>,
+                                       device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        let raw: Vec<ffi::compeg_region> = regions.iter().map(Region::raw).collect();
+        let pad = pad.map_or(ptr::null(), |p| p.as_ptr());
+        check(ffi::compeg_batch_pack_tensor_filtered(self.raw.as_ptr(), &spec.raw(), &filter.raw(), raw.as_ptr(), raw.len(), pad, device_dst,
+                                                     dst_bytes, stream.0))
     }
 
     pub fn wait(&mut self) -> Result<()> {

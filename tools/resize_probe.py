@@ -22,6 +22,11 @@ The regions arm (--regions; default table profiles/tensor_regions.txt), the same
 dst the whole output beside pack_tensor_resized of the same launch (the work is identical); the letterbox of 4K into
 640x640 beside the chain it replaces, a resized pack to 640x360 into a temporary and torch.nn.functional.pad; and 1024
 crops of 128x128 out of 16 4K frames in one call beside 1024 single Decoder.pack_tensor_resized calls.
+
+The filtered arm (--filtered; default table profiles/tensor_filtered.txt), the same method: Batch.pack_tensor_filtered
+with each of the four kernels, whole frames of 1080p and of 4K -> 224x224 in f16 at k = 1 and 4K at k = 8, beside the
+antialiased Batch.pack_tensor_regions of the same regions (the same arithmetic as the triangle arm: a lane per element
+against a lane per band of rows) and the decode of the same batch.
 """
 import argparse
 import os
@@ -259,6 +264,63 @@ def regions_arm(args, torch, F, compeg_amd, images_of, resident, gpu, stream):
     return "\n".join(lines) + "\n"
 
 
+# the filtered arm: (name, (width, height), output size, k)
+FILTERED_CONFIGS = (("1080p -> 224x224 f16 k=1", (1920, 1080), (224, 224), 1),
+                    ("4K -> 224x224 f16 k=1", (3840, 2160), (224, 224), 1),
+                    ("4K -> 224x224 f16 k=8", (3840, 2160), (224, 224), 8))
+
+
+def filtered_arm(args, torch, compeg_amd, images_of, resident, gpu, stream):
+    """The table of the filtered arm, as text."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import filter_reference as fr   # the header's contracts in numpy
+    n, handle = args.batch, stream.cuda_stream
+    scale = [1.0 / (255.0 * s) for s in STD]
+    bias = [-m / s for m, s in zip(MEAN, STD)]
+    kernels = list(compeg_amd.FILTER_KERNELS)
+    lines = [f"filtered tensor output: {n} resident 4:2:2 DRI=4 frames per configuration, decoded once; {gpu.name()}; library {os.path.relpath(compeg_amd.LIB_PATH, ROOT)}",
+             f"box .. lanczos3 = Batch.pack_tensor_filtered of whole frames; antialias = Batch.pack_tensor_regions(antialias=True) of the same regions "
+             f"(triangle's arithmetic, a lane per element); decode = Batch.decode of the same batch",
+             f"HIP events on one stream, the arms of a configuration launch by launch in turn, their order turning round from one repetition to the "
+             f"next, one untimed round in front; median of {args.reps} (min .. max), ms"]
+    verdicts = []
+    for name, (w, h), (ow, oh), k in FILTERED_CONFIGS:
+        items = images_of(w, h)
+        batch = resident([items[i % len(items)] for i in range(n)])
+        whole = [(i, None, None) for i in range(n)]
+        out = {key: torch.empty((n, 3, oh, ow), dtype=torch.float16, device="cuda") for key in kernels + ["antialias"]}
+        kw = dict(dtype="f16", downscale=k, scale=scale, bias=bias, hip_stream=handle)
+
+        def primer():
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < PRIME_SECONDS:
+                batch.decode(handle)
+                batch.wait()
+
+        arms = [(lambda key=key: batch.pack_tensor_filtered(out[key], (ow, oh), whole, kernel=key, **kw)) for key in kernels]
+        arms.append(lambda: batch.pack_tensor_regions(out["antialias"], (ow, oh), whole, antialias=True, **kw))
+        arms.append(lambda: batch.decode(handle))
+        t = _timed_in_turn(torch, stream, args.reps, primer, arms)
+        rgba = batch.read_output(0)
+        lines += ["", name]
+        for key, row in zip(kernels, t):
+            wrong = int((fr.expected(rgba, (ow, oh), k, "f16", scale, bias, "rgb", key) != out[key][0].cpu().numpy()).sum())
+            lines.append(f"  {key:<10} {_cell(row)}   slot 0: {wrong} elements off the contract")
+        equal = bool(torch.equal(out["triangle"].view(torch.int16), out["antialias"].view(torch.int16)))
+        lines.append(f"  {'antialias':<10} {_cell(t[4])}   all slots equal to triangle: {equal}")
+        lines.append(f"  {'decode':<10} {_cell(t[5])}")
+        tri, old = t[1], t[4]
+        ratio = statistics.median(old) / statistics.median(tri)
+        verdict = ("faster" if statistics.median(tri) < statistics.median(old) else "slower") if _gap(tri, old) else "within the rows' own spread"
+        lines.append(f"  triangle in bands against the antialiased pack: antialias/triangle {ratio:.2f}, {verdict}")
+        verdicts.append(f"{name}: {ratio:.2f} ({verdict})")
+        print("\n".join(lines[-9:]), file=sys.stderr, flush=True)   # (progress: the table itself is printed at the end)
+        del out, batch
+        torch.cuda.empty_cache()
+    lines += ["", "antialias/triangle: " + "; ".join(verdicts)]
+    return "\n".join(lines) + "\n"
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=256)
@@ -268,9 +330,10 @@ def main():
     p.add_argument("--out", default=None, help="default: profiles/tensor_resize.txt, or profiles/tensor_resize_antialias.txt with --antialias")
     p.add_argument("--antialias", action="store_true", help="the antialias arm instead of the table against the chain")
     p.add_argument("--regions", action="store_true", help="the regions arm (Batch.pack_tensor_regions) instead; default table profiles/tensor_regions.txt")
+    p.add_argument("--filtered", action="store_true", help="the filtered arm (Batch.pack_tensor_filtered) instead; default table profiles/tensor_filtered.txt")
     args = p.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "tensor_regions.txt" if args.regions else
+        args.out = os.path.join(ROOT, "profiles", "tensor_filtered.txt" if args.filtered else "tensor_regions.txt" if args.regions else
                                 "tensor_resize_antialias.txt" if args.antialias else "tensor_resize.txt")
 
     import torch
@@ -303,8 +366,9 @@ def main():
         batch.wait()
         return batch
 
-    if args.antialias or args.regions:
-        text = (regions_arm(args, torch, F, compeg_amd, images_of, resident, gpu, stream) if args.regions else
+    if args.antialias or args.regions or args.filtered:
+        text = (filtered_arm(args, torch, compeg_amd, images_of, resident, gpu, stream) if args.filtered else
+                regions_arm(args, torch, F, compeg_amd, images_of, resident, gpu, stream) if args.regions else
                 antialias_arm(args, torch, compeg_amd, images_of, resident, gpu, stream))
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
