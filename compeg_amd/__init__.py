@@ -18,12 +18,13 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
-                   LIB_PATH, METADATA_BYTES, Error, FilterSpec, Rect, Region, ResizeSpec, TensorSpec, check, lib)
+                   LIB_PATH, METADATA_BYTES, Error, FilterSpec, OrientedRegion, Rect, Region, ResizeSpec, TensorSpec, check, lib)
 
 __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Texture", "Error", "HostBuffer", "JpegList",
            "host_register", "host_unregister", "version", "LIB_PATH", "tensor_shape", "TENSOR_DTYPES", "TENSOR_ORDERS",
            "resized_tensor_shape", "RESIZE_FILTERS", "ResizeSpec", "Rect", "Region", "FIT_ALIGNS", "region_fit",
-           "region_tensor_shape", "FILTER_KERNELS", "FilterSpec", "filtered_tensor_shape"]
+           "region_tensor_shape", "FILTER_KERNELS", "FilterSpec", "filtered_tensor_shape", "ORIENTATIONS", "OrientedRegion",
+           "orient_rect", "oriented_tensor_shape"]
 
 
 # compeg_decoder_last_kernel / compeg_batch_last_kernel (include/compeg_hip.h: COMPEG_KERNEL_*)
@@ -173,6 +174,56 @@ def filtered_tensor_shape(width, height, size, region=None, kernel="bicubic", dt
     pw, ph, nbytes = C.c_uint32(), C.c_uint32(), C.c_size_t()
     check(lib.compeg_filtered_tensor_shape(C.byref(spec), C.byref(filter), width, height, C.byref(r) if r is not None else None,
                                            C.byref(pw), C.byref(ph), C.byref(nbytes)))
+    return (3, filter.out_height, filter.out_width), nbytes.value, (ph.value, pw.value)
+
+
+# Oriented tensor output (include/compeg_hip.h): the EXIF orientation values by name -- what has to be done to the stored
+# raster to see it upright
+ORIENTATIONS = {"normal": 1, "mirror": 2, "rotate180": 3, "flip": 4, "transpose": 5, "rotate90": 6, "transverse": 7, "rotate270": 8}
+
+
+def _orientation(orientation):
+    """0..8 from a name of ORIENTATIONS, "exif" (0: the image's own tag) or the number itself (which the library checks)."""
+    if isinstance(orientation, str):
+        if orientation == "exif":
+            return 0
+        if orientation not in ORIENTATIONS:
+            raise Error(f"unknown orientation {orientation!r} (\"exif\" or one of {', '.join(ORIENTATIONS)})")
+        return ORIENTATIONS[orientation]
+    return orientation
+
+
+def _oriented_regions(regions, orientation):
+    """compeg_oriented_region list from (image, src, dst) or (image, src, dst, orientation) tuples (or OrientedRegions as they
+    are); `orientation` is for the regions that carry none."""
+    out = []
+    for region in regions:
+        if not isinstance(region, OrientedRegion):
+            r = OrientedRegion()
+            r.region = _region(tuple(region)[:3])
+            r.orientation, r.reserved = _orientation(region[3] if len(region) > 3 else orientation), 0
+            region = r
+        out.append(region)
+    return (OrientedRegion * max(len(out), 1))(*out), len(out)
+
+
+def orient_rect(upright_size, orientation, rect):
+    """(x, y, w, h) in the stored raster of rect = (x, y, w, h) of the upright image of upright_size = (w, h): what goes
+    into a region's src when the crop was chosen on the upright image (compeg_orient_rect; no device needed)."""
+    stored = Rect()
+    check(lib.compeg_orient_rect(upright_size[0], upright_size[1], _orientation(orientation), C.byref(_rect(rect)), C.byref(stored)))
+    return stored.x, stored.y, stored.width, stored.height
+
+
+def oriented_tensor_shape(width, height, size, region=None, orientation=1, kernel="bicubic", dtype="f16", downscale=1):
+    """((3, oh, ow), bytes, (ph, pw)) of one slot of an oriented pack: filtered_tensor_shape for pack_tensor_oriented --
+    width x height the stored raster, size = (ow, oh) the upright slot, region = (image, src, dst[, orientation]); the
+    tap limit is taken along the stored axes (compeg_oriented_tensor_shape; no device needed; "exif" counts as 1)."""
+    spec = _tensor_spec(dtype, downscale, (1, 1, 1), (0, 0, 0), "rgb")
+    filter = _filter_spec(size, kernel)
+    list_, _ = _oriented_regions([region if region is not None else (0, None, None)], orientation)
+    pw, ph, nbytes = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    check(lib.compeg_oriented_tensor_shape(C.byref(spec), C.byref(filter), width, height, list_, C.byref(pw), C.byref(ph), C.byref(nbytes)))
     return (3, filter.out_height, filter.out_width), nbytes.value, (ph.value, pw.value)
 
 
@@ -329,6 +380,11 @@ class ImageData:
 
     def parallelism(self):
         return lib.compeg_image_parallelism(self._h)
+
+    @property
+    def orientation(self):
+        """Extension (compeg_image_orientation): the file's EXIF orientation tag, 1..8; 1 where it has no usable one."""
+        return lib.compeg_image_orientation(self._h)
 
     # what the reference uploads for this image (src/lib.rs:397-407)
     def metadata(self):
@@ -545,6 +601,20 @@ class Decoder:
         check(lib.compeg_decoder_pack_tensor_filtered(self._h, C.byref(spec), C.byref(filter), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
                                                       C.c_void_p(hip_stream)))
 
+    def pack_tensor_oriented(self, dst, size, regions=None, orientation="exif", kernel="bicubic", pad=(0, 0, 0), dtype="f16", downscale=1,
+                             scale=(1, 1, 1), bias=(0, 0, 0), order="rgb", hip_stream=0):
+        """Extension (compeg_decoder_pack_tensor_oriented): pack_tensor_filtered with an orientation per region -- a name of
+        ORIENTATIONS, 1..8, or "exif" for the image's own tag.  size = (ow, oh) is the UPRIGHT slot, a region's dst lies in
+        it, its src in the stored raster (orient_rect maps an upright crop there); regions are (0, src, dst) or
+        (0, src, dst, orientation), `orientation` serving those that carry none.  regions=None: the whole image into the whole
+        output.  Returns without waiting, like pack_tensor."""
+        spec = _tensor_spec(dtype, downscale, scale, bias, order)
+        filter = _filter_spec(size, kernel)
+        list_, n = _oriented_regions(regions if regions is not None else [(0, None, None)], orientation)
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_decoder_pack_tensor_oriented(self._h, C.byref(spec), C.byref(filter), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
+                                                      C.c_void_p(hip_stream)))
+
     def read_coefficients(self, total_dus):
         out = np.empty(total_dus * 32, dtype=np.int32)
         check(lib.compeg_decoder_read_coefficients(self._h, out.ctypes.data, out.size))
@@ -674,6 +744,24 @@ class Batch:
         addr, nbytes = _device_range(dst)
         check(lib.compeg_batch_pack_tensor_filtered(self._h, C.byref(spec), C.byref(filter), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
                                                     C.c_void_p(hip_stream)))
+
+    def pack_tensor_oriented(self, dst, size, regions=None, orientation="exif", kernel="bicubic", pad=(0, 0, 0), dtype="f16", downscale=1,
+                             scale=(1, 1, 1), bias=(0, 0, 0), order="rgb", hip_stream=0):
+        """Extension (compeg_batch_pack_tensor_oriented): Decoder.pack_tensor_oriented over the last decode's images, regions
+        (image, src, dst) or (image, src, dst, orientation).  regions=None: every image, whole, into its own upright slot,
+        [count, 3, oh, ow].  Returns without waiting; wait() covers it."""
+        spec = _tensor_spec(dtype, downscale, scale, bias, order)
+        filter = _filter_spec(size, kernel)
+        list_, n = _oriented_regions(regions if regions is not None else [(i, None, None) for i in range(self.count())], orientation)
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_batch_pack_tensor_oriented(self._h, C.byref(spec), C.byref(filter), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
+                                                    C.c_void_p(hip_stream)))
+
+    def orientation(self, index):
+        """The EXIF orientation tag (1..8) of image `index` of the last upload (compeg_batch_image_orientation)."""
+        out = C.c_uint32()
+        check(lib.compeg_batch_image_orientation(self._h, index, C.byref(out)))
+        return out.value
 
     def algorithmic_bytes(self):
         return lib.compeg_batch_algorithmic_bytes(self._h)

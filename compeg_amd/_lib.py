@@ -49,6 +49,12 @@ class FilterSpec(C.Structure):
     _fields_ = [("out_width", C.c_uint32), ("out_height", C.c_uint32), ("kernel", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class OrientedRegion(C.Structure):
+    """compeg_oriented_region (include/compeg_hip.h, "Oriented tensor output"): a Region whose dst lies in the upright
+    slot, and the orientation (0: the image's own EXIF tag; 1..8: the EXIF values) under which its slot is written."""
+    _fields_ = [("region", Region), ("orientation", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -138,6 +144,12 @@ def _load():
         "compeg_filtered_tensor_shape": (i, [C.POINTER(TensorSpec), C.POINTER(FilterSpec), u32, u32, C.POINTER(Region), pu32, pu32, psz]),
         "compeg_decoder_pack_tensor_filtered": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(Region), sz, C.POINTER(C.c_float), vp, sz, vp]),
         "compeg_batch_pack_tensor_filtered": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(Region), sz, C.POINTER(C.c_float), vp, sz, vp]),
+        "compeg_image_orientation": (u32, [vp]),
+        "compeg_batch_image_orientation": (i, [vp, sz, pu32]),
+        "compeg_orient_rect": (i, [u32, u32, u32, C.POINTER(Rect), C.POINTER(Rect)]),
+        "compeg_oriented_tensor_shape": (i, [C.POINTER(TensorSpec), C.POINTER(FilterSpec), u32, u32, C.POINTER(OrientedRegion), pu32, pu32, psz]),
+        "compeg_decoder_pack_tensor_oriented": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(OrientedRegion), sz, C.POINTER(C.c_float), vp, sz, vp]),
+        "compeg_batch_pack_tensor_oriented": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(OrientedRegion), sz, C.POINTER(C.c_float), vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("COMPEG_LIB") and not hasattr(L, name):

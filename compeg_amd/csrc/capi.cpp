@@ -291,8 +291,24 @@ int check_filter_spec(const compeg_filter_spec *filter)
     return COMPEG_OK;
 }
 
-// One region of a filtered call: check_region with the kernel's tap limit, n * 2S <= 128 * o both ways against the
-// inner extent, in place of the antialias flag's.
+// The kernel's tap limit for a checked region, n * 2S <= 128 * o both ways against the inner extent; `note`: what the
+// message adds behind the extents.
+int check_filter_taps(const compeg_region *out, const compeg_tensor_spec *spec, const compeg_filter_spec *filter, const std::string &which,
+                      const std::string &note)
+{
+    static const char *const names[] = {"box", "triangle", "bicubic", "lanczos3"};
+    static const uint32_t twice_support[] = {1u, 2u, 4u, 6u}, most[] = {128u, 64u, 32u, 21u};
+    const uint32_t pw = out->src.width / spec->downscale, ph = out->src.height / spec->downscale, s2 = twice_support[filter->kernel];
+    if (uint64_t(pw) * s2 > 128u * uint64_t(out->dst.width) || uint64_t(ph) * s2 > 128u * uint64_t(out->dst.height))
+        return fail(COMPEG_E_INVALID_ARG, ("filter: " + which + names[filter->kernel] + " reduces by " + std::to_string(most[filter->kernel]) +
+                                           " at the most either way, " + std::to_string(pw) + "x" + std::to_string(ph) + " to " +
+                                           std::to_string(out->dst.width) + "x" + std::to_string(out->dst.height) + " is more" + note +
+                                           ": choose a larger downscale")
+                                              .c_str());
+    return COMPEG_OK;
+}
+
+// One region of a filtered call: check_region with the kernel's tap limit in place of the antialias flag's.
 int check_filtered_region(const compeg_region *region, const compeg_tensor_spec *spec, const compeg_filter_spec *filter, uint32_t width,
                           uint32_t height, const std::string &which, compeg_region *out)
 {
@@ -300,15 +316,43 @@ int check_filtered_region(const compeg_region *region, const compeg_tensor_spec 
     const int rc = check_region(region, spec, &extent, width, height, which, out);
     if (rc != COMPEG_OK)
         return rc;
-    static const char *const names[] = {"box", "triangle", "bicubic", "lanczos3"};
-    static const uint32_t twice_support[] = {1u, 2u, 4u, 6u}, most[] = {128u, 64u, 32u, 21u};
-    const uint32_t pw = out->src.width / spec->downscale, ph = out->src.height / spec->downscale, s2 = twice_support[filter->kernel];
-    if (uint64_t(pw) * s2 > 128u * uint64_t(out->dst.width) || uint64_t(ph) * s2 > 128u * uint64_t(out->dst.height))
-        return fail(COMPEG_E_INVALID_ARG, ("filter: " + which + names[filter->kernel] + " reduces by " + std::to_string(most[filter->kernel]) +
-                                           " at the most either way, " + std::to_string(pw) + "x" + std::to_string(ph) + " to " +
-                                           std::to_string(out->dst.width) + "x" + std::to_string(out->dst.height) + " is more: choose a larger downscale")
-                                              .c_str());
-    return COMPEG_OK;
+    return check_filter_taps(out, spec, filter, which, "");
+}
+
+// One region of an oriented call whose stored image is WxH and carries the tag image_orientation: `out` is the region
+// with src resolved, dst replaced by dst' (inside T, include/compeg_hip.h) and the orientation 1..8.  The messages about
+// dst speak of it as the caller gave it, in the upright output.
+int check_oriented_region(const compeg_oriented_region *region, const compeg_tensor_spec *spec, const compeg_filter_spec *filter, uint32_t width,
+                          uint32_t height, uint32_t image_orientation, const std::string &which, compeg_oriented_region *out)
+{
+    const compeg_oriented_region whole{};
+    const compeg_oriented_region &g = region ? *region : whole;
+    if (g.reserved != 0u || g.region.reserved != 0u)
+        return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "reserved must be 0").c_str());
+    if (g.orientation > 8u)
+        return fail(COMPEG_E_INVALID_ARG, ("orient: " + which + "orientation " + std::to_string(g.orientation) +
+                                           " is none of 0 (the image's own tag), 1 .. 8 (the EXIF values)").c_str());
+    const uint32_t o = g.orientation == COMPEG_ORIENT_FROM_IMAGE ? image_orientation : g.orientation;
+    const uint32_t ow = filter->out_width, oh = filter->out_height;
+    const compeg_rect &d = g.region.dst;
+    const bool dst_whole = !d.x && !d.y && !d.width && !d.height;
+    const compeg_rect upright = dst_whole ? compeg_rect{0, 0, ow, oh} : d;
+    const std::string text = std::to_string(upright.width) + "x" + std::to_string(upright.height);
+    if (upright.width == 0u || upright.height == 0u)
+        return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "dst " + text + " has a side of 0").c_str());
+    compeg_region turned = g.region;
+    if (!compeg::orient_rect(ow, oh, o, upright, turned.dst))
+        return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "dst " + text + " at (" + std::to_string(upright.x) + ", " + std::to_string(upright.y) +
+                                           ") leaves the " + std::to_string(ow) + "x" + std::to_string(oh) + " output").c_str());
+    const bool transposes = o >= 5u;
+    const compeg_resize_spec extent{transposes ? oh : ow, transposes ? ow : oh, COMPEG_RESIZE_BILINEAR, 0u}; // T's (no flag: no ratio check there)
+    const int rc = check_region(&turned, spec, &extent, width, height, which, &out->region);
+    if (rc != COMPEG_OK)
+        return rc;
+    out->orientation = o;
+    out->reserved = 0u;
+    return check_filter_taps(&out->region, spec, filter, which,
+                             transposes ? " (orientation " + std::to_string(o) + " transposes: the crop's width goes against dst's height)" : "");
 }
 
 // What both filtered packs check before they look at their object: the specs, the list, the pad.
@@ -1550,6 +1594,164 @@ int compeg_batch_pack_tensor_filtered(compeg_batch *batch, const compeg_tensor_s
         }
         const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
         Status s = batch->pack_tensor_filtered(*spec, *filter, list.data(), count, pad_copy, device_dst,
+                                               hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream);
+        return s.ok() ? ok() : fail(s);
+    });
+}
+
+/* ---- Oriented tensor output ------------------------------------------------ */
+
+uint32_t compeg_image_orientation(const compeg_image *img)
+{
+    return img ? img->data->orientation : 1u;
+}
+
+int compeg_batch_image_orientation(const compeg_batch *batch, size_t index, uint32_t *out)
+{
+    return guarded([&] {
+        if (!batch)
+            return fail(COMPEG_E_INVALID_ARG, "batch is NULL");
+        if (!out)
+            return fail(COMPEG_E_INVALID_ARG, "out is NULL");
+        if (index >= batch->count || index >= batch->orientations.size())
+            return fail(COMPEG_E_INVALID_ARG, ("orient: image " + std::to_string(index) + " is beyond the batch's " +
+                                               std::to_string(batch->count) + " images").c_str());
+        *out = batch->orientations[index];
+        return ok();
+    });
+}
+
+int compeg_orient_rect(uint32_t upright_width, uint32_t upright_height, uint32_t orientation, const compeg_rect *upright,
+                       compeg_rect *stored)
+{
+    return guarded([&] {
+        if (!upright || !stored)
+            return fail(COMPEG_E_INVALID_ARG, "orient: a rectangle pointer is NULL");
+        if (orientation < 1u || orientation > 8u)
+            return fail(COMPEG_E_INVALID_ARG, ("orient: orientation " + std::to_string(orientation) + " is none of 1 .. 8 (the EXIF values)").c_str());
+        compeg_rect r{};
+        if (!compeg::orient_rect(upright_width, upright_height, orientation, *upright, r))
+            return fail(COMPEG_E_INVALID_ARG, ("orient: rectangle " + std::to_string(upright->width) + "x" + std::to_string(upright->height) + " at (" +
+                                               std::to_string(upright->x) + ", " + std::to_string(upright->y) + ") leaves the " +
+                                               std::to_string(upright_width) + "x" + std::to_string(upright_height) + " image").c_str());
+        *stored = r;
+        return ok();
+    });
+}
+
+int compeg_oriented_tensor_shape(const compeg_tensor_spec *spec, const compeg_filter_spec *filter, uint32_t width, uint32_t height,
+                                 const compeg_oriented_region *region, uint32_t *pre_width, uint32_t *pre_height, size_t *bytes_per_slot)
+{
+    return guarded([&] {
+        size_t elem = 0;
+        int rc = check_tensor_spec(spec, &elem);
+        if (rc == COMPEG_OK)
+            rc = check_filter_spec(filter);
+        compeg_oriented_region r{};
+        if (rc == COMPEG_OK)
+            rc = check_oriented_region(region, spec, filter, width, height, 1u, "", &r);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (pre_width)
+            *pre_width = r.region.src.width / spec->downscale;
+        if (pre_height)
+            *pre_height = r.region.src.height / spec->downscale;
+        if (bytes_per_slot)
+            *bytes_per_slot = size_t(3) * size_t(filter->out_height) * size_t(filter->out_width) * elem;
+        return ok();
+    });
+}
+
+int compeg_decoder_pack_tensor_oriented(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
+                                        const compeg_oriented_region *regions, size_t count, const float *pad, void *device_dst,
+                                        size_t dst_bytes, void *hip_stream)
+{
+    return guarded([&] {
+        // (what does not depend on the object first: it is checked where no device is)
+        size_t elem = 0, bytes = 0;
+        int rc = check_filtered_call(spec, filter, regions ? &regions->region : nullptr, count, pad, &elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (!dec)
+            return fail(COMPEG_E_INVALID_ARG, "dec is NULL");
+        if (!dec->have_last || !dec->out.ptr)
+            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
+        const compeg_resize_spec extent{filter->out_width, filter->out_height, COMPEG_RESIZE_BILINEAR, 0u};
+        if (!region_tensor_bytes(&extent, elem, count, &bytes))
+            return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
+        // (the launch's limits and the destination before the list is copied: nothing is allocated for a count no call
+        // takes.  Which slot shapes the list needs takes the orientations alone; one above 8 is the list's check to name)
+        bool upright = false, transposed = false;
+        for (size_t r = 0; r < count; r++) {
+            const uint32_t o = regions[r].orientation == COMPEG_ORIENT_FROM_IMAGE ? dec->last_orientation : regions[r].orientation;
+            (o < 5u ? upright : transposed) = true;
+        }
+        if (count > 0xffffffffull || !compeg::orient_grid_fits(uint32_t(count), *spec, *filter, upright, transposed))
+            return fail(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
+        rc = check_tensor_destination(device_dst, dst_bytes, bytes, elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        // (the copy of the caller's list: src as a whole rectangle, dst as dst', the orientation 1..8)
+        std::vector<compeg_oriented_region> list(count);
+        for (size_t r = 0; r < count; r++) {
+            const std::string which = "region " + std::to_string(r) + ": ";
+            if (regions[r].region.image != 0u)
+                return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "image " + std::to_string(regions[r].region.image) + ", a decoder has image 0 only").c_str());
+            rc = check_oriented_region(regions + r, spec, filter, dec->last_w, dec->last_h, dec->last_orientation, which, &list[r]);
+            if (rc != COMPEG_OK)
+                return rc;
+        }
+        const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
+        Status s = dec->pack_tensor_oriented(*spec, *filter, list.data(), count, pad_copy, device_dst,
+                                             hip_stream ? static_cast<hipStream_t>(hip_stream) : dec->gpu->stream);
+        return s.ok() ? ok() : fail(s);
+    });
+}
+
+int compeg_batch_pack_tensor_oriented(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
+                                      const compeg_oriented_region *regions, size_t count, const float *pad, void *device_dst,
+                                      size_t dst_bytes, void *hip_stream)
+{
+    return guarded([&] {
+        // (what does not depend on the object first: it is checked where no device is)
+        size_t elem = 0, bytes = 0;
+        int rc = check_filtered_call(spec, filter, regions ? &regions->region : nullptr, count, pad, &elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (!batch)
+            return fail(COMPEG_E_INVALID_ARG, "batch is NULL");
+        if (!batch->count || !batch->output_decoded)
+            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
+        const compeg_resize_spec extent{filter->out_width, filter->out_height, COMPEG_RESIZE_BILINEAR, 0u};
+        if (!region_tensor_bytes(&extent, elem, count, &bytes))
+            return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
+        // (the launch's limits and the destination before the list is copied, as for a decoder)
+        bool upright = false, transposed = false;
+        for (size_t r = 0; r < count; r++) {
+            const uint32_t i = regions[r].region.image;
+            const uint32_t tag = i < batch->orientations.size() ? batch->orientations[i] : 1u;
+            const uint32_t o = regions[r].orientation == COMPEG_ORIENT_FROM_IMAGE ? tag : regions[r].orientation;
+            (o < 5u ? upright : transposed) = true;
+        }
+        if (count > 0xffffffffull || !compeg::orient_grid_fits(uint32_t(count), *spec, *filter, upright, transposed))
+            return fail(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
+        rc = check_tensor_destination(device_dst, dst_bytes, bytes, elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        std::vector<compeg_oriented_region> list(count);
+        for (size_t r = 0; r < count; r++) {
+            const std::string which = "region " + std::to_string(r) + ": ";
+            const uint32_t i = regions[r].region.image;
+            if (i >= batch->count)
+                return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "image " + std::to_string(i) + " is beyond the batch's " +
+                                                   std::to_string(batch->count) + " images").c_str());
+            const uint32_t tag = i < batch->orientations.size() ? batch->orientations[i] : 1u;
+            rc = check_oriented_region(regions + r, spec, filter, batch->descs[i].out_w, batch->descs[i].out_h, tag, which, &list[r]);
+            if (rc != COMPEG_OK)
+                return rc;
+        }
+        const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
+        Status s = batch->pack_tensor_oriented(*spec, *filter, list.data(), count, pad_copy, device_dst,
                                                hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream);
         return s.ok() ? ok() : fail(s);
     });

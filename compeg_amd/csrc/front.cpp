@@ -244,6 +244,43 @@ HuffmanLut HuffmanLut::annex_k(int which)
     return t;
 }
 
+uint32_t exif_orientation(const uint8_t *payload, size_t len, bool *is_exif)
+{
+    const bool exif = len >= 6 && memcmp(payload, "Exif\0\0", 6) == 0;
+    if (is_exif)
+        *is_exif = exif;
+    if (!exif)
+        return 1;
+    // (offsets count from the TIFF header)
+    const uint8_t *tiff = payload + 6;
+    const size_t n = len - 6;
+    if (n < 8)
+        return 1;
+    bool little;
+    if (memcmp(tiff, "II*\0", 4) == 0)
+        little = true;
+    else if (memcmp(tiff, "MM\0*", 4) == 0)
+        little = false;
+    else
+        return 1;
+    const auto u16 = [&](size_t at) { return little ? uint32_t(tiff[at]) | uint32_t(tiff[at + 1]) << 8 : uint32_t(tiff[at]) << 8 | uint32_t(tiff[at + 1]); };
+    const auto u32 = [&](size_t at) { return little ? u16(at) | u16(at + 2) << 16 : u16(at) << 16 | u16(at + 2); };
+    const size_t ifd = u32(4);
+    if (ifd > n || n - ifd < 2)
+        return 1;
+    const size_t entries = u16(ifd);
+    for (size_t e = 0; e < entries; e++) {
+        const size_t at = ifd + 2 + e * 12; // (65535 entries of 12 bytes behind a 32-bit offset: no wrap in size_t)
+        if (at > n || n - at < 12)
+            return 1;
+        if (u16(at) != 0x0112u)
+            continue;
+        const uint32_t value = u16(at + 8);
+        return u16(at + 2) == 3u && u32(at + 4) == 1u && value >= 1u && value <= 8u ? value : 1u;
+    }
+    return 1;
+}
+
 Status ImageData::parse(const uint8_t *jpeg, size_t len, bool copy, ImageData **out, unsigned flags)
 {
     *out = nullptr;
@@ -278,7 +315,7 @@ Status ImageData::parse(const uint8_t *jpeg, size_t len, bool copy, ImageData **
     Metadata &md = img->metadata;
     memset(&md, 0, sizeof md);
 
-    bool have_frame = false, have_scan = false, have_dri = false;
+    bool have_frame = false, have_scan = false, have_dri = false, have_exif = false;
     uint32_t dri = 0;
     uint8_t frame_ids[3] = {0, 0, 0}, hv[3] = {0, 0, 0}, tq[3] = {0, 0, 0};
     uint8_t td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
@@ -457,6 +494,9 @@ Status ImageData::parse(const uint8_t *jpeg, size_t len, bool copy, ImageData **
                 if (seg.left() < size_t(f[7]) * f[8] * 3)
                     return malformed(kEof);
             }
+        } else if (marker == 0xe1 && !have_scan && !have_exif) {
+            // APP1: only looked at, for the orientation tag; nothing in it is an error
+            img->orientation = exif_orientation(jpeg + seg.at, seg.left(), &have_exif);
         }
         // every other segment (APPn, COM, unknown) is skipped by its length
         file.at = resume;

@@ -77,6 +77,9 @@ struct ImageData {
     // parsed with kParseDeferScanEnd and the file ends with EOI: the segment was taken to run up to that EOI without
     // walking it (whoever preprocesses it has to see that no other marker lies inside: scan_kernels.hip, flag bit 1)
     bool scan_end_deferred = false;
+    // The EXIF orientation tag (1..8; 1: no usable tag) of the first APP1 "Exif" segment in front of the scan.  It never
+    // changes what parse() accepts, rejects or says.
+    uint32_t orientation = 1;
 
     const uint8_t *scan_data() const { return jpeg + scan_offset; }
     uint32_t total_mcus() const
@@ -88,5 +91,11 @@ struct ImageData {
     // flags: COMPEG_PARSE_* (compeg_hip.h); 0 = exactly the reference's accept / reject behaviour
     static Status parse(const uint8_t *jpeg, size_t len, bool copy, ImageData **out, unsigned flags = 0);
 };
+
+// The orientation tag (0x0112) of an APP1 payload of `len` bytes: "Exif\0\0", a TIFF header ("II*\0" or "MM\0*"), IFD0 at
+// the header's offset, 12-byte entries; the entry with the tag, type 3 (SHORT) and count 1, its value in the file's byte
+// order.  Every read is checked against len; whatever does not fit -- no "Exif", a short segment, an offset outside it,
+// another type or count, a value outside 1..8 -- gives 1.  `is_exif`: whether the payload begins "Exif\0\0".
+uint32_t exif_orientation(const uint8_t *payload, size_t len, bool *is_exif);
 
 } // namespace compeg

@@ -167,6 +167,19 @@ bool filter_grid_fits(uint32_t slots, const compeg_tensor_spec &spec, const comp
 hipError_t launch_filter_tensor(const void *device_blob, size_t tables_at, uint32_t slots, const compeg_tensor_spec &spec,
                                 const compeg_filter_spec &filter, const float *pad, void *dst, hipStream_t stream);
 
+// Oriented tensor output (orient_kernels.hip, orient_body.h): the filtered pack's lane with an EXIF orientation per slot;
+// `slots` records of kOrientRecordBytes and the axis tables behind them, as one blob.  ow x oh: the upright slot.
+constexpr size_t kOrientRecordBytes = 56;
+// False: what make_filter_blob refuses, an orientation outside 1..8 or a dst' outside T (the caller has checked them).
+bool make_orient_blob(std::vector<uint32_t> &blob, size_t &tables_at, const OrientSource *sources, uint32_t slots, uint32_t k,
+                      uint32_t kernel, uint32_t ow, uint32_t oh);
+// upright / transposed: whether some slot has an orientation in 1..4 / in 5..8; a slot's lanes are the larger count.
+bool orient_grid_fits(uint32_t slots, const compeg_tensor_spec &spec, const compeg_filter_spec &filter, bool upright, bool transposed);
+// pad: three values on the pixel scale by source channel (R, G, B), or null for zeros.
+hipError_t launch_orient_tensor(const void *device_blob, size_t tables_at, uint32_t slots, const compeg_tensor_spec &spec,
+                                const compeg_filter_spec &filter, bool upright, bool transposed, const float *pad, void *dst,
+                                hipStream_t stream);
+
 #if defined(CG_AC_STAMPS)
 // diagnostic build: AC-loop cycle counters (kernels_body.h)
 hipError_t read_ac_stamps(unsigned long long out[4], bool reset);

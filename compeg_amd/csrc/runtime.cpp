@@ -841,6 +841,7 @@ Status compeg_decoder::enqueue(const ImageData &img, hipStream_t stream, bool *c
     last_md = md;
     last_w = img.width;
     last_h = img.height;
+    last_orientation = img.orientation;
     last_desc_dev = db;
     have_last = true;
 
@@ -1218,8 +1219,10 @@ void compeg_batch::note_batch_properties(const ImageData *const *images, size_t 
     //   walks -- they depend on the selectors, the entropy mode and the zero-stream data units as well.  Its flat grid
     //   needs walk_shared (walk_state_shared, desc.cpp) on top of `uniform`.
     uniform = n > 0;
+    orientations.resize(n);
     for (size_t i = 0; i < n; i++) {
         const ImageData &img = *images[i], &first = *images[0];
+        orientations[i] = img.orientation;
         generic_layout = generic_layout || !is_422(img);
         if (img.metadata.components[0].hsample != layout_h || img.metadata.components[0].vsample != layout_v)
             layout_h = layout_v = 0; // (mixed samplings in one batch)
@@ -2517,6 +2520,76 @@ Status compeg_batch::pack_tensor_filtered(const compeg_tensor_spec &spec, const 
     const void *device_records = nullptr;
     CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &device_records));
     CG_HIP(launch_filter_tensor(device_records, tables_at, uint32_t(count), spec, filter, pad, dst, stream));
+    // (no timing events; the next decode on another stream records decode_done on last_stream, behind this)
+    last_stream = stream;
+    return Status{};
+}
+
+// Oriented tensor output: pack_tensor_filtered's ordering and staging with the orient kernels' records and launch.
+// Which of the two slot shapes a list needs: T is the upright extent (1..4) or the transposed one (5..8).
+static void orient_shapes(const compeg_oriented_region *regions, size_t count, bool &upright, bool &transposed)
+{
+    upright = transposed = false;
+    for (size_t r = 0; r < count; r++)
+        (regions[r].orientation < 5u ? upright : transposed) = true;
+}
+
+Status compeg_decoder::pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_oriented_region *regions,
+                                            size_t count, const float *pad, void *dst, hipStream_t stream)
+{
+    CG_HIP(hipSetDevice(gpu->device));
+    bool upright = false, transposed = false;
+    orient_shapes(regions, count, upright, transposed);
+    // (the limits first: nothing is allocated for a count that no launch takes)
+    if (count > 0xffffffffull || !orient_grid_fits(uint32_t(count), spec, filter, upright, transposed))
+        return Status::error(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
+    std::vector<OrientSource> placements(count);
+    for (size_t r = 0; r < count; r++)
+        placements[r] = OrientSource{RegionSource{out.ptr, uint32_t(out_pitch), regions[r].region.src, regions[r].region.dst}, regions[r].orientation};
+    std::vector<uint32_t> blob;
+    size_t tables_at = 0;
+    if (!make_orient_blob(blob, tables_at, placements.data(), uint32_t(count), spec.downscale, filter.kernel, filter.out_width, filter.out_height))
+        return Status::error(COMPEG_E_INVALID_ARG, kFilterNoBlob);
+    if (!decode_done)
+        CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
+    if (decode_pending && stream != last_stream)
+        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
+    const void *records = nullptr;
+    CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &records));
+    CG_HIP(launch_orient_tensor(records, tables_at, uint32_t(count), spec, filter, upright, transposed, pad, dst, stream));
+    CG_HIP(hipEventRecord(decode_done, stream));
+    decode_pending = true;
+    last_stream = stream;
+    return Status{};
+}
+
+Status compeg_batch::pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_oriented_region *regions,
+                                          size_t count, const float *pad, void *dst, hipStream_t stream)
+{
+    CG_HIP(hipSetDevice(gpu->device));
+    bool upright = false, transposed = false;
+    orient_shapes(regions, count, upright, transposed);
+    // (the limits first: nothing is allocated for a count that no launch takes)
+    if (count > 0xffffffffull || !orient_grid_fits(uint32_t(count), spec, filter, upright, transposed))
+        return Status::error(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
+    std::vector<OrientSource> placements(count);
+    for (size_t r = 0; r < count; r++) {
+        const ImageDesc &d = descs[regions[r].region.image];
+        placements[r] = OrientSource{RegionSource{d.out, d.out_pitch, regions[r].region.src, regions[r].region.dst}, regions[r].orientation};
+    }
+    std::vector<uint32_t> blob;
+    size_t tables_at = 0;
+    if (!make_orient_blob(blob, tables_at, placements.data(), uint32_t(count), spec.downscale, filter.kernel, filter.out_width, filter.out_height))
+        return Status::error(COMPEG_E_INVALID_ARG, kFilterNoBlob);
+    if (decode_recorded && stream != last_stream) {
+        if (!decode_done)
+            CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
+        CG_HIP(hipEventRecord(decode_done, last_stream));
+        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
+    }
+    const void *device_records = nullptr;
+    CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &device_records));
+    CG_HIP(launch_orient_tensor(device_records, tables_at, uint32_t(count), spec, filter, upright, transposed, pad, dst, stream));
     // (no timing events; the next decode on another stream records decode_done on last_stream, behind this)
     last_stream = stream;
     return Status{};

@@ -120,6 +120,7 @@ struct compeg_decoder {
     compeg::Metadata last_md{};
     bool have_last = false;
     uint32_t last_w = 0, last_h = 0; // the last image's own extent (out_w x out_h never shrink)
+    uint32_t last_orientation = 1;   // ... and its EXIF orientation tag (front.h)
     compeg::HuffLdsPlan last_plan{};
     uint32_t last_span = 0;
     bool coefficients_valid = false; // ac/dc hold the last image's coefficients
@@ -161,6 +162,10 @@ struct compeg_decoder {
                                        size_t count, const float *pad, void *dst, hipStream_t stream);
     // Filtered tensor output: pack_tensor_regions with one of the four resampling kernels (the tap limit checked by the caller too)
     compeg::Status pack_tensor_filtered(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_region *regions,
+                                        size_t count, const float *pad, void *dst, hipStream_t stream);
+    // Oriented tensor output: pack_tensor_filtered through an orientation per slot; every region's dst is dst' (inside T) and
+    // its orientation 1..8 by now (checked by the caller, like everything else)
+    compeg::Status pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_oriented_region *regions,
                                         size_t count, const float *pad, void *dst, hipStream_t stream);
     compeg::Status check_scan_result(bool &fell_back);
     compeg::Status preprocess_on_device(const compeg::ImageData &img, hipStream_t stream, uint32_t &nwords,
@@ -269,4 +274,9 @@ struct compeg_batch {
     // Filtered tensor output: pack_tensor_regions with one of the four resampling kernels (the tap limit checked by the caller too)
     compeg::Status pack_tensor_filtered(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_region *regions,
                                         size_t count, const float *pad, void *dst, hipStream_t stream);
+    // Oriented tensor output: pack_tensor_filtered through an orientation per slot; every region's dst is dst' (inside T) and
+    // its orientation 1..8 by now (checked by the caller, like everything else)
+    compeg::Status pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_oriented_region *regions,
+                                        size_t count, const float *pad, void *dst, hipStream_t stream);
+    std::vector<uint32_t> orientations; // the EXIF orientation tag of every image of the last upload (note_batch_properties)
 };

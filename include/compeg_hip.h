@@ -546,6 +546,72 @@ int compeg_batch_pack_tensor_filtered(compeg_batch *batch, const compeg_tensor_s
                                       const compeg_filter_spec *filter, const compeg_region *regions, size_t count,
                                       const float *pad, void *device_dst, size_t dst_bytes, void *hip_stream);
 
+/* ---- Oriented tensor output (extension) --------------------------------------
+ * compeg_*_pack_tensor_filtered with an orientation per region: the EXIF values 1..8 (tag 0x0112) -- so a frame whose
+ * file says "rotate me" reaches the model upright, and a crop is mirrored where it is packed -- in the same one pass.
+ * New entry points beside the old ones: no existing call does anything different.
+ *
+ * The tag.  compeg_image_orientation gives an image's: read from the first APP1 segment in front of SOS whose payload
+ * begins "Exif\0\0" -- TIFF header "II*\0" or "MM\0*", IFD0 at the header's offset, entries of 12 bytes, the entry with
+ * tag 0x0112, type 3 (SHORT) and count 1, its value in the file's byte order.  Every read is checked against the
+ * segment's length; whatever does not fit (a short segment, an offset outside it, another type or count, a value
+ * outside 1..8) gives 1, and so does a file without such a segment.  The tag never changes what compeg_image_parse*
+ * accepts or rejects, nor any message.  compeg_batch_image_orientation: the same for image `index` of the last upload,
+ * whichever way it was uploaded.  A decoder remembers the tag of the image it decoded last.
+ *
+ * Contract (exact).  Destination [count][3][oh][ow], tight, (ow, oh) = filter's out_width x out_height: the UPRIGHT
+ * slot.  Let o be the region's orientation, COMPEG_ORIENT_FROM_IMAGE replaced by the image's tag.  Let the slot T have
+ * the extent (ow', oh') = (ow, oh) for o in 1..4 and (oh, ow) for o in 5..8.  T is, bit for bit, what
+ * compeg_*_pack_tensor_filtered stores for the region {image, src, dst'} at the output extent ow' x oh' with the same
+ * spec, kernel and pad; src is in the coordinates of the stored raster (compeg_orient_rect maps an upright rectangle
+ * there), dst = (dx, dy, dw, dh) in those of the upright slot.  The slot written is U = orient_o(T), every plane alike:
+ *   o   U[y][x] =                dst' =                            PIL's Image.transpose
+ *   1   T[y][x]                  (dx, dy, dw, dh)                  none
+ *   2   T[y][ow-1-x]             (ow-dx-dw, dy, dw, dh)            FLIP_LEFT_RIGHT
+ *   3   T[oh-1-y][ow-1-x]        (ow-dx-dw, oh-dy-dh, dw, dh)      ROTATE_180
+ *   4   T[oh-1-y][x]             (dx, oh-dy-dh, dw, dh)            FLIP_TOP_BOTTOM
+ *   5   T[x][y]                  (dy, dx, dh, dw)                  TRANSPOSE
+ *   6   T[ow-1-x][y]             (dy, ow-dx-dw, dh, dw)            ROTATE_270
+ *   7   T[ow-1-x][oh-1-y]        (oh-dy-dh, ow-dx-dw, dh, dw)      TRANSVERSE
+ *   8   T[x][oh-1-y]             (oh-dy-dh, dx, dh, dw)            ROTATE_90
+ * (what PIL's ImageOps.exif_transpose does for a file with that tag).  What follows: orientation 1 is the filtered pack,
+ * bit for bit; every element of every slot is written exactly once and no byte outside the tensor is written; the pad
+ * fills the image of what it fills in T; the resampling runs along the stored axes; the tap limit n * 2S <= 128 * o is
+ * taken against T's axes -- for o in 5..8 pw against dh and ph against dw. */
+#define COMPEG_ORIENT_FROM_IMAGE 0 /* the image's own tag (compeg_image_orientation) */
+typedef struct compeg_oriented_region {
+    compeg_region region;           /* image, src (stored coordinates), dst (in the upright slot) */
+    uint32_t orientation, reserved; /* 0..8; reserved = 0 */
+} compeg_oriented_region;           /* 48 bytes */
+/* 1..8; 1 for NULL. */
+uint32_t compeg_image_orientation(const compeg_image *img);
+/* COMPEG_E_INVALID_ARG: batch or out NULL, index beyond the last upload. */
+int compeg_batch_image_orientation(const compeg_batch *batch, size_t index, uint32_t *out);
+/* No device needed: the rectangle of the stored raster that holds the pixels of `upright`, a rectangle of the upright
+ * image of upright_width x upright_height: the map dst -> dst' of the table with the upright extents for (ow, oh), in
+ * 64-bit integers.  COMPEG_E_INVALID_ARG for an orientation outside 1..8, a NULL pointer, a rectangle that leaves the
+ * image. */
+int compeg_orient_rect(uint32_t upright_width, uint32_t upright_height, uint32_t orientation, const compeg_rect *upright,
+                       compeg_rect *stored);
+/* No device needed: compeg_filtered_tensor_shape for the oriented calls; width x height: the stored raster.  There is no
+ * image here, so COMPEG_ORIENT_FROM_IMAGE counts as 1.  COMPEG_E_INVALID_ARG for what compeg_filtered_tensor_shape
+ * rejects of spec, filter and {src, dst'} at T's extent, and for: an orientation above 8, reserved != 0 (either one).
+ * Beyond the tap limit under a transposing orientation the message says that the orientation transposes. */
+int compeg_oriented_tensor_shape(const compeg_tensor_spec *spec, const compeg_filter_spec *filter, uint32_t width,
+                                 uint32_t height, const compeg_oriented_region *region, uint32_t *pre_width,
+                                 uint32_t *pre_height, size_t *bytes_per_slot);
+/* Like compeg_*_pack_tensor_filtered in everything they say about hip_stream, ordering, timing events, the decoder's
+ * texture, compeg_batch_wait, the copies made before the call returns, the messages and the rejections, with
+ * compeg_oriented_tensor_shape's in place of compeg_filtered_tensor_shape's. */
+int compeg_decoder_pack_tensor_oriented(compeg_decoder *dec, const compeg_tensor_spec *spec,
+                                        const compeg_filter_spec *filter, const compeg_oriented_region *regions,
+                                        size_t count, const float *pad, void *device_dst, size_t dst_bytes,
+                                        void *hip_stream);
+int compeg_batch_pack_tensor_oriented(compeg_batch *batch, const compeg_tensor_spec *spec,
+                                      const compeg_filter_spec *filter, const compeg_oriented_region *regions,
+                                      size_t count, const float *pad, void *device_dst, size_t dst_bytes,
+                                      void *hip_stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

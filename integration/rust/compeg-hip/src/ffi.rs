@@ -75,6 +75,16 @@ pub struct compeg_filter_spec {
     pub reserved: u32,
 }
 
+/// One output slot of `compeg_*_pack_tensor_oriented` (compeg_hip.h, "Oriented tensor output"): a region whose `dst`
+/// lies in the upright slot, and the EXIF orientation (1..8; 0: the image's own tag) under which the slot is written.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct compeg_oriented_region {
+    pub region: compeg_region,
+    pub orientation: u32,
+    pub reserved: u32,
+}
+
 pub const COMPEG_OK: c_int = 0;
 pub const COMPEG_E_INVALID_ARG: c_int = -1;
 pub const COMPEG_E_UNSUPPORTED: c_int = -2;
@@ -108,6 +118,8 @@ pub const COMPEG_FILTER_BOX: u32 = 0;
 pub const COMPEG_FILTER_TRIANGLE: u32 = 1;
 pub const COMPEG_FILTER_BICUBIC: u32 = 2;
 pub const COMPEG_FILTER_LANCZOS3: u32 = 3;
+/// `compeg_oriented_region::orientation`: the image's own tag (`compeg_image_orientation`).
+pub const COMPEG_ORIENT_FROM_IMAGE: u32 = 0;
 
 extern "C" {
     pub fn compeg_last_error() -> *const c_char;
@@ -246,5 +258,22 @@ extern "C" {
     pub fn compeg_batch_pack_tensor_filtered(batch: *mut compeg_batch, spec: *const compeg_tensor_spec,
                                              filter: *const compeg_filter_spec, regions: *const compeg_region, count: usize,
                                              pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
+                                             hip_stream: *mut c_void) -> c_int;
+
+    // Oriented tensor output (extension)
+    pub fn compeg_image_orientation(img: *const compeg_image) -> u32;
+    pub fn compeg_batch_image_orientation(batch: *const compeg_batch, index: usize, out: *mut u32) -> c_int;
+    pub fn compeg_orient_rect(upright_width: u32, upright_height: u32, orientation: u32, upright: *const compeg_rect,
+                              stored: *mut compeg_rect) -> c_int;
+    pub fn compeg_oriented_tensor_shape(spec: *const compeg_tensor_spec, filter: *const compeg_filter_spec, width: u32, height: u32,
+                                        region: *const compeg_oriented_region, pre_width: *mut u32, pre_height: *mut u32,
+                                        bytes_per_slot: *mut usize) -> c_int;
+    pub fn compeg_decoder_pack_tensor_oriented(dec: *mut compeg_decoder, spec: *const compeg_tensor_spec,
+                                               filter: *const compeg_filter_spec, regions: *const compeg_oriented_region,
+                                               count: usize, pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
+                                               hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_batch_pack_tensor_oriented(batch: *mut compeg_batch, spec: *const compeg_tensor_spec,
+                                             filter: *const compeg_filter_spec, regions: *const compeg_oriented_region,
+                                             count: usize, pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
                                              hip_stream: *mut c_void) -> c_int;
 }

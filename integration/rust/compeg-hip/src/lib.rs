@@ -256,6 +256,59 @@ impl FilterSpec {
     }
 }
 
+/// The orientation of one slot of an oriented pack (compeg_hip.h, "Oriented tensor output"): the EXIF values, named by
+/// what has to be done to the stored raster to see it upright, or `Exif` for the image's own tag.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Orientation {
+    Exif = 0,
+    Normal = 1,
+    Mirror = 2,
+    Rotate180 = 3,
+    Flip = 4,
+    Transpose = 5,
+    Rotate90 = 6,
+    Transverse = 7,
+    Rotate270 = 8,
+}
+
+impl Orientation {
+    /// The orientation of an EXIF value 1..8 (`ImageData::orientation`); anything else is `Normal`.
+    pub fn from_tag(tag: u32) -> Self {
+        use Orientation::*;
+        [Normal, Normal, Mirror, Rotate180, Flip, Transpose, Rotate90, Transverse, Rotate270].get(tag as usize).copied().unwrap_or(Normal)
+    }
+
+    /// The rectangle of the stored raster that holds the pixels of `upright`, a rectangle of the upright image of
+    /// `size` = (width, height): what goes into `Region::src` for a crop chosen on the upright image.  Not for `Exif`.
+    pub fn stored_rect(self, size: (u32, u32), upright: &Rect) -> Result<Rect> {
+        let mut r = Rect { x: 0, y: 0, width: 0, height: 0 };
+        check(unsafe { ffi::compeg_orient_rect(size.0, size.1, self as u32, upright, &mut r) })?;
+        Ok(r)
+    }
+}
+
+/// One output slot of `Decoder::pack_tensor_oriented` / `Batch::pack_tensor_oriented`: `region.src` in the stored raster,
+/// `region.dst` in the upright slot.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct OrientedRegion {
+    pub region: Region,
+    pub orientation: Orientation,
+}
+
+impl OrientedRegion {
+    fn raw(&self) -> ffi::compeg_oriented_region {
+        ffi::compeg_oriented_region { region: self.region.raw(), orientation: self.orientation as u32, reserved: 0 }
+    }
+
+    /// `(pre_width, pre_height, bytes)`: `FilterSpec::shape` for the oriented calls -- `filter`'s extent is the upright
+    /// slot, the tap limit is taken along the stored axes; `Exif` counts as `Normal` here.  No device needed.
+    pub fn shape(&self, tensor: &TensorSpec, filter: &FilterSpec, width: u32, height: u32) -> Result<(u32, u32, usize)> {
+        let (mut w, mut h, mut n) = (0, 0, 0);
+        check(unsafe { ffi::compeg_oriented_tensor_shape(&tensor.raw(), &filter.raw(), width, height, &self.raw(), &mut w, &mut h, &mut n) })?;
+        Ok((w, h, n))
+    }
+}
+
 /// Device + stream + loaded gfx950 code object.  Immutable after creation and
 /// reference-counted inside the library; share it as `Arc<Gpu>` like the reference.
 pub struct Gpu {
@@ -358,6 +411,11 @@ impl<'a> ImageData<'a> {
     /// Number of restart intervals = lanes that decode in parallel.
     pub fn parallelism(&self) -> u32 {
         unsafe { ffi::compeg_image_parallelism(self.raw.as_ptr()) }
+    }
+
+    /// Extension: the file's EXIF orientation tag, 1..8; 1 where it has no usable one.
+    pub fn orientation(&self) -> u32 {
+        unsafe { ffi::compeg_image_orientation(self.raw.as_ptr()) }
     }
 }
 
@@ -532,6 +590,18 @@ impl Decoder {
         let raw: Vec<ffi::compeg_region> = regions.iter().map(Region::raw).collect();
         let pad = pad.map_or(ptr::null(), |p| p.as_ptr());
         check(ffi::compeg_decoder_pack_tensor_filtered(self.raw.as_ptr(), &spec.raw(), &filter.raw(), raw.as_ptr(), raw.len(), pad, device_dst,
+                                                       dst_bytes, stream.0))
+    }
+
+    /// Extension: `pack_tensor_filtered` with an orientation per region; `filter`'s extent is the upright slot.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn pack_tensor_oriented(&mut self, spec: &TensorSpec, filter: &FilterSpec, regions: &[OrientedRegion], pad: Option<&[f32; 3]>,
+                                       device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        let raw: Vec<ffi::compeg_oriented_region> = regions.iter().map(OrientedRegion::raw).collect();
+        let pad = pad.map_or(ptr::null(), |p| p.as_ptr());
+        check(ffi::compeg_decoder_pack_tensor_oriented(self.raw.as_ptr(), &spec.raw(), &filter.raw(), raw.as_ptr(), raw.len(), pad, device_dst,
                                                        dst_bytes, stream.0))
     }
 
@@ -735,6 +805,26 @@ impl Batch {
         let pad = pad.map_or(ptr::null(), |p| p.as_ptr());
         check(ffi::compeg_batch_pack_tensor_filtered(self.raw.as_ptr(), &spec.raw(), &filter.raw(), raw.as_ptr(), raw.len(), pad, device_dst,
                                                      dst_bytes, stream.0))
+    }
+
+    /// Records on `stream` the oriented pack of the last decode: `pack_tensor_filtered` with an orientation per region;
+    /// `filter`'s extent is the upright slot.  `wait` covers it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn pack_tensor_oriented(&mut self, spec: &TensorSpec, filter: &FilterSpec, regions: &[OrientedRegion], pad: Option<&[f32; 3]>,
+                                       device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        let raw: Vec<ffi::compeg_oriented_region> = regions.iter().map(OrientedRegion::raw).collect();
+        let pad = pad.map_or(ptr::null(), |p| p.as_ptr());
+        check(ffi::compeg_batch_pack_tensor_oriented(self.raw.as_ptr(), &spec.raw(), &filter.raw(), raw.as_ptr(), raw.len(), pad, device_dst,
+                                                     dst_bytes, stream.0))
+    }
+
+    /// The EXIF orientation tag (1..8) of image `index` of the last upload.
+    pub fn orientation(&self, index: usize) -> Result<u32> {
+        let mut o = 0;
+        check(unsafe { ffi::compeg_batch_image_orientation(self.raw.as_ptr(), index, &mut o) })?;
+        Ok(o)
     }
 
     pub fn wait(&mut self) -> Result<()> {

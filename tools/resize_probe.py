@@ -27,6 +27,11 @@ The filtered arm (--filtered; default table profiles/tensor_filtered.txt), the s
 with each of the four kernels, whole frames of 1080p and of 4K -> 224x224 in f16 at k = 1 and 4K at k = 8, beside the
 antialiased Batch.pack_tensor_regions of the same regions (the same arithmetic as the triangle arm: a lane per element
 against a lane per band of rows) and the decode of the same batch.
+
+The oriented arm (--oriented; default table profiles/tensor_oriented.txt), the same method: Batch.pack_tensor_oriented of
+whole frames -> 224x224, bicubic, k = 1, at the orientations 1, 2 and 6, beside Batch.pack_tensor_filtered and the chains
+a user writes without it: the filtered pack into a temporary, then torch.rot90(t, -1, (2, 3)).contiguous() for
+orientation 6, t.flip(3) for orientation 2.
 """
 import argparse
 import os
@@ -321,6 +326,74 @@ def filtered_arm(args, torch, compeg_amd, images_of, resident, gpu, stream):
     return "\n".join(lines) + "\n"
 
 
+# the oriented arm: (name, (width, height), element type, orientations)
+ORIENTED_CONFIGS = (("1080p -> 224x224 f16 k=1", (1920, 1080), "f16", (1, 2, 6)),
+                    ("4K -> 224x224 f16 k=1", (3840, 2160), "f16", (1, 2, 6)),
+                    ("1080p -> 224x224 u8 k=1", (1920, 1080), "u8", (6,)),      # runs of 8 bytes
+                    ("1080p -> 224x224 f32 k=1", (1920, 1080), "f32", (6,)))    # runs of 32 bytes
+
+
+def oriented_arm(args, torch, compeg_amd, images_of, resident, gpu, stream):
+    """The table of the oriented arm, as text."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import orient_reference as orf   # the header's contract in numpy
+    n, handle, (ow, oh) = args.batch, stream.cuda_stream, (224, 224)
+    torch_type = {"u8": torch.uint8, "f16": torch.float16, "f32": torch.float32}
+    lines = [f"oriented tensor output: {n} resident 4:2:2 DRI=4 frames per configuration, decoded once; {gpu.name()}; library {os.path.relpath(compeg_amd.LIB_PATH, ROOT)}",
+             "filtered = Batch.pack_tensor_filtered of whole frames, bicubic; o=N = Batch.pack_tensor_oriented of the same regions at orientation N; "
+             "chain 6 = the filtered pack into a temporary, then torch.rot90(t, -1, (2, 3)).contiguous(); chain 2 = the same, then t.flip(3)",
+             f"HIP events on one stream, the arms of a configuration launch by launch in turn, their order turning round from one repetition to the "
+             f"next, one untimed round in front; median of {args.reps} (min .. max), ms"]
+    verdicts = []
+    for name, (w, h), dtype, orientations in ORIENTED_CONFIGS:
+        items = images_of(w, h)
+        batch = resident([items[i % len(items)] for i in range(n)])
+        whole = [(i, None, None) for i in range(n)]
+        scale = [1.0] * 3 if dtype == "u8" else [1.0 / (255.0 * s) for s in STD]
+        bias = [0.0] * 3 if dtype == "u8" else [-m / s for m, s in zip(MEAN, STD)]
+        kw = dict(kernel="bicubic", dtype=dtype, scale=scale, bias=bias, hip_stream=handle)
+        keys = ["filtered"] + [f"o={o}" for o in orientations] + [f"chain {o}" for o in orientations if o != 1]
+        out = {key: torch.empty((n, 3, oh, ow), dtype=torch_type[dtype], device="cuda") for key in keys + ["tmp"]}
+
+        def primer():
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < PRIME_SECONDS:
+                batch.decode(handle)
+                batch.wait()
+
+        def chain(o):
+            batch.pack_tensor_filtered(out["tmp"], (ow, oh), whole, **kw)
+            out[f"chain {o}"] = torch.rot90(out["tmp"], -1, (2, 3)).contiguous() if o == 6 else out["tmp"].flip(3)
+
+        arms = [lambda: batch.pack_tensor_filtered(out["filtered"], (ow, oh), whole, **kw)]
+        arms += [(lambda o=o: batch.pack_tensor_oriented(out[f"o={o}"], (ow, oh), whole, orientation=o, **kw)) for o in orientations]
+        arms += [(lambda o=o: chain(o)) for o in orientations if o != 1]
+        t = dict(zip(keys, _timed_in_turn(torch, stream, args.reps, primer, arms)))
+        rgba = batch.read_output(0)
+        lines += ["", name]
+        for key in keys:
+            o = 1 if key == "filtered" else int(key.split("=")[-1].split()[-1])
+            note = ""
+            if not key.startswith("chain"):
+                wrong = int((orf.expected(rgba, (ow, oh), 1, dtype, scale, bias, "rgb", "bicubic", o=o) != out[key][0].cpu().numpy()).sum())
+                note = f"   slot 0: {wrong} elements off the contract"
+            else:
+                note = f"   all slots equal to o={o}: {bool(torch.equal(out[key], out[f'o={o}']))}"
+            lines.append(f"  {key:<10} {_cell(t[key])}{note}")
+        for o in orientations:
+            other = "filtered" if o != 6 else "chain 6"
+            a, b = t[f"o={o}"], t[other]
+            ratio = statistics.median(a) / statistics.median(b)
+            verdict = ("faster" if statistics.median(a) < statistics.median(b) else "slower") if _gap(a, b) else "within the rows' own spread"
+            lines.append(f"  o={o} against {other}: {ratio:.2f}, {verdict}")
+            verdicts.append(f"{name}: o={o}/{other} {ratio:.2f} ({verdict})")
+        print("\n".join(lines[-(len(keys) + len(orientations) + 1):]), file=sys.stderr, flush=True)   # (progress: the table itself is printed at the end)
+        del out, batch
+        torch.cuda.empty_cache()
+    lines += [""] + verdicts
+    return "\n".join(lines) + "\n"
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=256)
@@ -331,9 +404,10 @@ def main():
     p.add_argument("--antialias", action="store_true", help="the antialias arm instead of the table against the chain")
     p.add_argument("--regions", action="store_true", help="the regions arm (Batch.pack_tensor_regions) instead; default table profiles/tensor_regions.txt")
     p.add_argument("--filtered", action="store_true", help="the filtered arm (Batch.pack_tensor_filtered) instead; default table profiles/tensor_filtered.txt")
+    p.add_argument("--oriented", action="store_true", help="the oriented arm (Batch.pack_tensor_oriented) instead; default table profiles/tensor_oriented.txt")
     args = p.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "tensor_filtered.txt" if args.filtered else "tensor_regions.txt" if args.regions else
+        args.out = os.path.join(ROOT, "profiles", "tensor_oriented.txt" if args.oriented else "tensor_filtered.txt" if args.filtered else "tensor_regions.txt" if args.regions else
                                 "tensor_resize_antialias.txt" if args.antialias else "tensor_resize.txt")
 
     import torch
@@ -366,8 +440,9 @@ def main():
         batch.wait()
         return batch
 
-    if args.antialias or args.regions or args.filtered:
-        text = (filtered_arm(args, torch, compeg_amd, images_of, resident, gpu, stream) if args.filtered else
+    if args.antialias or args.regions or args.filtered or args.oriented:
+        text = (oriented_arm(args, torch, compeg_amd, images_of, resident, gpu, stream) if args.oriented else
+                filtered_arm(args, torch, compeg_amd, images_of, resident, gpu, stream) if args.filtered else
                 regions_arm(args, torch, F, compeg_amd, images_of, resident, gpu, stream) if args.regions else
                 antialias_arm(args, torch, compeg_amd, images_of, resident, gpu, stream))
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
