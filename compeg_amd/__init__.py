@@ -18,13 +18,14 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
-                   LIB_PATH, METADATA_BYTES, Error, FilterSpec, OrientedRegion, Rect, Region, ResizeSpec, TensorSpec, check, lib)
+                   LIB_PATH, METADATA_BYTES, Error, FilterSpec, NhwcSpec, OrientedRegion, Rect, Region, ResizeSpec, TensorSpec, check,
+                   lib)
 
 __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Texture", "Error", "HostBuffer", "JpegList",
            "host_register", "host_unregister", "version", "LIB_PATH", "tensor_shape", "TENSOR_DTYPES", "TENSOR_ORDERS",
            "resized_tensor_shape", "RESIZE_FILTERS", "ResizeSpec", "Rect", "Region", "FIT_ALIGNS", "region_fit",
            "region_tensor_shape", "FILTER_KERNELS", "FilterSpec", "filtered_tensor_shape", "ORIENTATIONS", "OrientedRegion",
-           "orient_rect", "oriented_tensor_shape"]
+           "orient_rect", "oriented_tensor_shape", "NhwcSpec", "nhwc_tensor_shape"]
 
 
 # compeg_decoder_last_kernel / compeg_batch_last_kernel (include/compeg_hip.h: COMPEG_KERNEL_*)
@@ -246,6 +247,73 @@ def _device_range(dst):
             raise Error("pack_tensor: the destination must be contiguous")
         return int(cai["data"][0]), int(np.prod(shape, dtype=np.int64)) * itemsize
     raise Error("pack_tensor: dst is neither (address, nbytes), a tensor, nor a __cuda_array_interface__ object")
+
+
+def _nhwc_spec(channels, fill):
+    """compeg_nhwc_spec; the library checks the values."""
+    spec = NhwcSpec()
+    spec.channels, spec.fill = channels, float(fill)
+    spec.reserved[0] = spec.reserved[1] = 0
+    return spec
+
+
+def nhwc_tensor_shape(width, height, size, region=None, orientation=1, channels=3, fill=0.0, kernel="bicubic", dtype="f16", downscale=1):
+    """((oh, ow, C), bytes, (ph, pw)) of one slot of a channels-last pack: oriented_tensor_shape for pack_tensor_nhwc, with
+    C = channels, 3 or 4 (compeg_nhwc_tensor_shape; no device needed)."""
+    spec = _tensor_spec(dtype, downscale, (1, 1, 1), (0, 0, 0), "rgb")
+    filter = _filter_spec(size, kernel)
+    nhwc = _nhwc_spec(channels, fill)
+    list_, _ = _oriented_regions([region if region is not None else (0, None, None)], orientation)
+    pw, ph, nbytes = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    check(lib.compeg_nhwc_tensor_shape(C.byref(spec), C.byref(filter), C.byref(nhwc), width, height, list_, C.byref(pw), C.byref(ph), C.byref(nbytes)))
+    return (filter.out_height, filter.out_width, nhwc.channels), nbytes.value, (ph.value, pw.value)
+
+
+def _nhwc_device_range(dst, size, channels):
+    """(address, bytes) of a channels-last pack destination of size = (ow, oh) and `channels`: _device_range's forms, with a
+    tensor taken by its shape and strides instead of is_contiguous() -- it must cover its memory densely, without overlap,
+    and be [.., oh, ow, C] row-major or [.., C, oh, ow] with channels-last strides (what torch.channels_last gives).  A
+    planar tensor is an error here, not a scrambled image.  No framework is imported for it."""
+    if isinstance(dst, tuple) and len(dst) == 2:
+        return int(dst[0]), int(dst[1])
+    if hasattr(dst, "data_ptr") and hasattr(dst, "stride") and hasattr(dst, "shape") and hasattr(dst, "element_size"):
+        address, itemsize = int(dst.data_ptr()), int(dst.element_size())
+        shape, strides = tuple(int(n) for n in dst.shape), tuple(int(n) for n in dst.stride())
+    else:
+        cai = getattr(dst, "__cuda_array_interface__", None)
+        if cai is None:
+            raise Error("pack_tensor_nhwc: dst is neither (address, nbytes), a tensor, nor a __cuda_array_interface__ object")
+        address, itemsize = int(cai["data"][0]), np.dtype(cai["typestr"]).itemsize
+        shape = tuple(int(n) for n in cai["shape"])
+        if cai.get("strides") is None:
+            strides = tuple(int(np.prod(shape[i + 1:], dtype=np.int64)) for i in range(len(shape)))
+        else:
+            if any(int(b) % itemsize for b in cai["strides"]):
+                raise Error("pack_tensor_nhwc: the destination's strides are no multiples of its element size")
+            strides = tuple(int(b) // itemsize for b in cai["strides"])
+    ow, oh = size
+    what = f"shape {shape} with strides {strides}"
+    if len(shape) < 3 or any(n < 1 for n in shape):
+        raise Error(f"pack_tensor_nhwc: the destination has {what}, neither [.., {oh}, {ow}, {channels}] nor [.., {channels}, {oh}, {ow}]")
+    # dense and without overlap: by ascending stride, each one is the extent of what lies below it (an axis of 1: any stride)
+    below = 1
+    for stride, n in sorted((s, n) for s, n in zip(strides, shape) if n != 1):
+        if stride != below:
+            raise Error(f"pack_tensor_nhwc: the destination ({what}) does not cover its memory densely (a slice, an expanded or an overlapping view)")
+        below *= n
+    lead = shape[:-3]
+    outer = [int(np.prod(lead[i + 1:], dtype=np.int64)) * oh * ow * channels for i in range(len(lead))]
+
+    def laid(inner):
+        return all(n == 1 or s == want for n, s, want in zip(shape, strides, outer + inner))
+    last = shape[-3:] == (oh, ow, channels) and laid([ow * channels, channels, 1])
+    first = shape[-3:] == (channels, oh, ow) and laid([1, ow * channels, channels])
+    if not (last or first):
+        planar = shape[-3:] == (channels, oh, ow)
+        raise Error(f"pack_tensor_nhwc: the destination has {what}: " +
+                    ("planar memory -- give it channels-last strides (torch: memory_format=torch.channels_last)" if planar else
+                     f"neither [.., {oh}, {ow}, {channels}] row-major nor [.., {channels}, {oh}, {ow}] with channels-last strides"))
+    return address, below * itemsize
 
 
 def _host_view(data):
@@ -615,6 +683,20 @@ class Decoder:
         check(lib.compeg_decoder_pack_tensor_oriented(self._h, C.byref(spec), C.byref(filter), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
                                                       C.c_void_p(hip_stream)))
 
+    def pack_tensor_nhwc(self, dst, size, regions=None, orientation="exif", channels=3, fill=0.0, kernel="bicubic", pad=(0, 0, 0), dtype="f16",
+                         downscale=1, scale=(1, 1, 1), bias=(0, 0, 0), order="rgb", hip_stream=0):
+        """Extension (compeg_decoder_pack_tensor_nhwc): pack_tensor_oriented into a channels-last destination,
+        [count, oh, ow, channels] with channels 3 or 4; element 3 of every pixel is `fill`, converted like any value, with
+        neither scale nor bias.  dst: (address, nbytes), a contiguous [.., oh, ow, C] tensor, or a [.., C, oh, ow] tensor with
+        channels-last strides (torch.channels_last) as it is -- a planar tensor is refused.  Returns without waiting."""
+        spec = _tensor_spec(dtype, downscale, scale, bias, order)
+        filter = _filter_spec(size, kernel)
+        nhwc = _nhwc_spec(channels, fill)
+        list_, n = _oriented_regions(regions if regions is not None else [(0, None, None)], orientation)
+        addr, nbytes = _nhwc_device_range(dst, size, channels)
+        check(lib.compeg_decoder_pack_tensor_nhwc(self._h, C.byref(spec), C.byref(filter), C.byref(nhwc), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
+                                                  C.c_void_p(hip_stream)))
+
     def read_coefficients(self, total_dus):
         out = np.empty(total_dus * 32, dtype=np.int32)
         check(lib.compeg_decoder_read_coefficients(self._h, out.ctypes.data, out.size))
@@ -756,6 +838,19 @@ class Batch:
         addr, nbytes = _device_range(dst)
         check(lib.compeg_batch_pack_tensor_oriented(self._h, C.byref(spec), C.byref(filter), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
                                                     C.c_void_p(hip_stream)))
+
+    def pack_tensor_nhwc(self, dst, size, regions=None, orientation="exif", channels=3, fill=0.0, kernel="bicubic", pad=(0, 0, 0), dtype="f16",
+                         downscale=1, scale=(1, 1, 1), bias=(0, 0, 0), order="rgb", hip_stream=0):
+        """Extension (compeg_batch_pack_tensor_nhwc): Decoder.pack_tensor_nhwc over the last decode's images, regions as in
+        pack_tensor_oriented.  regions=None: every image, whole, into its own upright slot, [count, oh, ow, channels].
+        Returns without waiting; wait() covers it."""
+        spec = _tensor_spec(dtype, downscale, scale, bias, order)
+        filter = _filter_spec(size, kernel)
+        nhwc = _nhwc_spec(channels, fill)
+        list_, n = _oriented_regions(regions if regions is not None else [(i, None, None) for i in range(self.count())], orientation)
+        addr, nbytes = _nhwc_device_range(dst, size, channels)
+        check(lib.compeg_batch_pack_tensor_nhwc(self._h, C.byref(spec), C.byref(filter), C.byref(nhwc), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
+                                                C.c_void_p(hip_stream)))
 
     def orientation(self, index):
         """The EXIF orientation tag (1..8) of image `index` of the last upload (compeg_batch_image_orientation)."""

@@ -55,6 +55,12 @@ class OrientedRegion(C.Structure):
     _fields_ = [("region", Region), ("orientation", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class NhwcSpec(C.Structure):
+    """compeg_nhwc_spec (include/compeg_hip.h, "Channels-last tensor output"): 3 or 4 channels a pixel, and the value of
+    the fourth."""
+    _fields_ = [("channels", C.c_uint32), ("fill", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -150,6 +156,9 @@ def _load():
         "compeg_oriented_tensor_shape": (i, [C.POINTER(TensorSpec), C.POINTER(FilterSpec), u32, u32, C.POINTER(OrientedRegion), pu32, pu32, psz]),
         "compeg_decoder_pack_tensor_oriented": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(OrientedRegion), sz, C.POINTER(C.c_float), vp, sz, vp]),
         "compeg_batch_pack_tensor_oriented": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(OrientedRegion), sz, C.POINTER(C.c_float), vp, sz, vp]),
+        "compeg_nhwc_tensor_shape": (i, [C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(NhwcSpec), u32, u32, C.POINTER(OrientedRegion), pu32, pu32, psz]),
+        "compeg_decoder_pack_tensor_nhwc": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(NhwcSpec), C.POINTER(OrientedRegion), sz, C.POINTER(C.c_float), vp, sz, vp]),
+        "compeg_batch_pack_tensor_nhwc": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(NhwcSpec), C.POINTER(OrientedRegion), sz, C.POINTER(C.c_float), vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("COMPEG_LIB") and not hasattr(L, name):

@@ -355,6 +355,30 @@ int check_oriented_region(const compeg_oriented_region *region, const compeg_ten
                              transposes ? " (orientation " + std::to_string(o) + " transposes: the crop's width goes against dst's height)" : "");
 }
 
+// compeg_nhwc_spec as the header has it.
+int check_nhwc_spec(const compeg_nhwc_spec *nhwc)
+{
+    if (!nhwc)
+        return fail(COMPEG_E_INVALID_ARG, "nhwc is NULL");
+    if (nhwc->channels != 3u && nhwc->channels != 4u)
+        return fail(COMPEG_E_INVALID_ARG, ("nhwc: channels " + std::to_string(nhwc->channels) + " is neither 3 nor 4").c_str());
+    if (!std::isfinite(nhwc->fill))
+        return fail(COMPEG_E_INVALID_ARG, "nhwc: fill is not finite");
+    if (nhwc->reserved[0] != 0u || nhwc->reserved[1] != 0u)
+        return fail(COMPEG_E_INVALID_ARG, "nhwc: reserved must be 0");
+    return COMPEG_OK;
+}
+
+// The bytes of `count` slots of `channels` elements a pixel at the filter's output extent; false: size_t does not hold them.
+bool slot_tensor_bytes(const compeg_filter_spec *filter, size_t channels, size_t elem, size_t count, size_t *bytes)
+{
+    const size_t slot = channels * size_t(filter->out_height) * size_t(filter->out_width) * elem;
+    if (count > SIZE_MAX / slot)
+        return false;
+    *bytes = slot * count;
+    return true;
+}
+
 // What both filtered packs check before they look at their object: the specs, the list, the pad.
 int check_filtered_call(const compeg_tensor_spec *spec, const compeg_filter_spec *filter, const compeg_region *regions, size_t count,
                         const float *pad, size_t *elem_bytes)
@@ -1662,22 +1686,25 @@ int compeg_oriented_tensor_shape(const compeg_tensor_spec *spec, const compeg_fi
     });
 }
 
-int compeg_decoder_pack_tensor_oriented(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
-                                        const compeg_oriented_region *regions, size_t count, const float *pad, void *device_dst,
-                                        size_t dst_bytes, void *hip_stream)
+// compeg_decoder_pack_tensor_oriented (channels_last false: nhwc is not looked at) and compeg_decoder_pack_tensor_nhwc (true: nhwc as
+// the caller gave it, NULL included): one road, so that the two families check the same things in the same order.
+static int decoder_pack_oriented(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_filter_spec *filter, bool channels_last,
+                                 const compeg_nhwc_spec *nhwc, const compeg_oriented_region *regions, size_t count, const float *pad,
+                                 void *device_dst, size_t dst_bytes, void *hip_stream)
 {
     return guarded([&] {
         // (what does not depend on the object first: it is checked where no device is)
         size_t elem = 0, bytes = 0;
         int rc = check_filtered_call(spec, filter, regions ? &regions->region : nullptr, count, pad, &elem);
+        if (rc == COMPEG_OK && channels_last)
+            rc = check_nhwc_spec(nhwc);
         if (rc != COMPEG_OK)
             return rc;
         if (!dec)
             return fail(COMPEG_E_INVALID_ARG, "dec is NULL");
         if (!dec->have_last || !dec->out.ptr)
             return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
-        const compeg_resize_spec extent{filter->out_width, filter->out_height, COMPEG_RESIZE_BILINEAR, 0u};
-        if (!region_tensor_bytes(&extent, elem, count, &bytes))
+        if (!slot_tensor_bytes(filter, channels_last ? nhwc->channels : 3u, elem, count, &bytes))
             return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
         // (the launch's limits and the destination before the list is copied: nothing is allocated for a count no call
         // takes.  Which slot shapes the list needs takes the orientations alone; one above 8 is the list's check to name)
@@ -1702,28 +1729,39 @@ int compeg_decoder_pack_tensor_oriented(compeg_decoder *dec, const compeg_tensor
                 return rc;
         }
         const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
-        Status s = dec->pack_tensor_oriented(*spec, *filter, list.data(), count, pad_copy, device_dst,
-                                             hip_stream ? static_cast<hipStream_t>(hip_stream) : dec->gpu->stream);
+        const hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : dec->gpu->stream;
+        Status s = channels_last ? dec->pack_tensor_nhwc(*spec, *filter, *nhwc, list.data(), count, pad_copy, device_dst, stream)
+                                 : dec->pack_tensor_oriented(*spec, *filter, list.data(), count, pad_copy, device_dst, stream);
         return s.ok() ? ok() : fail(s);
     });
 }
 
-int compeg_batch_pack_tensor_oriented(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
-                                      const compeg_oriented_region *regions, size_t count, const float *pad, void *device_dst,
-                                      size_t dst_bytes, void *hip_stream)
+int compeg_decoder_pack_tensor_oriented(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
+                                        const compeg_oriented_region *regions, size_t count, const float *pad, void *device_dst,
+                                        size_t dst_bytes, void *hip_stream)
+{
+    return decoder_pack_oriented(dec, spec, filter, false, nullptr, regions, count, pad, device_dst, dst_bytes, hip_stream);
+}
+
+// compeg_batch_pack_tensor_oriented (channels_last false: nhwc is not looked at) and compeg_batch_pack_tensor_nhwc (true: nhwc as
+// the caller gave it, NULL included): one road, so that the two families check the same things in the same order.
+static int batch_pack_oriented(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_filter_spec *filter, bool channels_last,
+                               const compeg_nhwc_spec *nhwc, const compeg_oriented_region *regions, size_t count, const float *pad,
+                               void *device_dst, size_t dst_bytes, void *hip_stream)
 {
     return guarded([&] {
         // (what does not depend on the object first: it is checked where no device is)
         size_t elem = 0, bytes = 0;
         int rc = check_filtered_call(spec, filter, regions ? &regions->region : nullptr, count, pad, &elem);
+        if (rc == COMPEG_OK && channels_last)
+            rc = check_nhwc_spec(nhwc);
         if (rc != COMPEG_OK)
             return rc;
         if (!batch)
             return fail(COMPEG_E_INVALID_ARG, "batch is NULL");
         if (!batch->count || !batch->output_decoded)
             return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
-        const compeg_resize_spec extent{filter->out_width, filter->out_height, COMPEG_RESIZE_BILINEAR, 0u};
-        if (!region_tensor_bytes(&extent, elem, count, &bytes))
+        if (!slot_tensor_bytes(filter, channels_last ? nhwc->channels : 3u, elem, count, &bytes))
             return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
         // (the launch's limits and the destination before the list is copied, as for a decoder)
         bool upright = false, transposed = false;
@@ -1751,10 +1789,60 @@ int compeg_batch_pack_tensor_oriented(compeg_batch *batch, const compeg_tensor_s
                 return rc;
         }
         const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
-        Status s = batch->pack_tensor_oriented(*spec, *filter, list.data(), count, pad_copy, device_dst,
-                                               hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream);
+        const hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream;
+        Status s = channels_last ? batch->pack_tensor_nhwc(*spec, *filter, *nhwc, list.data(), count, pad_copy, device_dst, stream)
+                                 : batch->pack_tensor_oriented(*spec, *filter, list.data(), count, pad_copy, device_dst, stream);
         return s.ok() ? ok() : fail(s);
     });
+}
+
+int compeg_batch_pack_tensor_oriented(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
+                                      const compeg_oriented_region *regions, size_t count, const float *pad, void *device_dst,
+                                      size_t dst_bytes, void *hip_stream)
+{
+    return batch_pack_oriented(batch, spec, filter, false, nullptr, regions, count, pad, device_dst, dst_bytes, hip_stream);
+}
+
+/* ---- Channels-last tensor output ------------------------------------------- */
+
+int compeg_nhwc_tensor_shape(const compeg_tensor_spec *spec, const compeg_filter_spec *filter, const compeg_nhwc_spec *nhwc, uint32_t width,
+                             uint32_t height, const compeg_oriented_region *region, uint32_t *pre_width, uint32_t *pre_height,
+                             size_t *bytes_per_slot)
+{
+    return guarded([&] {
+        size_t elem = 0;
+        int rc = check_tensor_spec(spec, &elem);
+        if (rc == COMPEG_OK)
+            rc = check_filter_spec(filter);
+        if (rc == COMPEG_OK)
+            rc = check_nhwc_spec(nhwc);
+        compeg_oriented_region r{};
+        if (rc == COMPEG_OK)
+            rc = check_oriented_region(region, spec, filter, width, height, 1u, "", &r);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (pre_width)
+            *pre_width = r.region.src.width / spec->downscale;
+        if (pre_height)
+            *pre_height = r.region.src.height / spec->downscale;
+        if (bytes_per_slot)
+            *bytes_per_slot = size_t(filter->out_height) * size_t(filter->out_width) * size_t(nhwc->channels) * elem;
+        return ok();
+    });
+}
+
+int compeg_decoder_pack_tensor_nhwc(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
+                                    const compeg_nhwc_spec *nhwc, const compeg_oriented_region *regions, size_t count, const float *pad,
+                                    void *device_dst, size_t dst_bytes, void *hip_stream)
+{
+    return decoder_pack_oriented(dec, spec, filter, true, nhwc, regions, count, pad, device_dst, dst_bytes, hip_stream);
+}
+
+int compeg_batch_pack_tensor_nhwc(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
+                                  const compeg_nhwc_spec *nhwc, const compeg_oriented_region *regions, size_t count, const float *pad,
+                                  void *device_dst, size_t dst_bytes, void *hip_stream)
+{
+    return batch_pack_oriented(batch, spec, filter, true, nhwc, regions, count, pad, device_dst, dst_bytes, hip_stream);
 }
 
 } // extern "C"

@@ -180,6 +180,12 @@ hipError_t launch_orient_tensor(const void *device_blob, size_t tables_at, uint3
                                 const compeg_filter_spec &filter, bool upright, bool transposed, const float *pad, void *dst,
                                 hipStream_t stream);
 
+// Channels-last tensor output (nhwc_kernels.hip, nhwc_body.h): the oriented pack's blob (make_orient_blob) and grid
+// (orient_grid_fits), its lane with a pixel's 3 or 4 channel values stored next to each other; dst: [slots][oh][ow][C].
+hipError_t launch_nhwc_tensor(const void *device_blob, size_t tables_at, uint32_t slots, const compeg_tensor_spec &spec,
+                              const compeg_filter_spec &filter, const compeg_nhwc_spec &nhwc, bool upright, bool transposed, const float *pad,
+                              void *dst, hipStream_t stream);
+
 #if defined(CG_AC_STAMPS)
 // diagnostic build: AC-loop cycle counters (kernels_body.h)
 hipError_t read_ac_stamps(unsigned long long out[4], bool reset);

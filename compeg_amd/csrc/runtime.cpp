@@ -2525,7 +2525,8 @@ Status compeg_batch::pack_tensor_filtered(const compeg_tensor_spec &spec, const 
     return Status{};
 }
 
-// Oriented tensor output: pack_tensor_filtered's ordering and staging with the orient kernels' records and launch.
+// Oriented tensor output: pack_tensor_filtered's ordering and staging with the orient kernels' records and launch -- and
+// channels-last tensor output, the same road to the nhwc kernels' launch: pack_oriented with nhwc, null for the planes.
 // Which of the two slot shapes a list needs: T is the upright extent (1..4) or the transposed one (5..8).
 static void orient_shapes(const compeg_oriented_region *regions, size_t count, bool &upright, bool &transposed)
 {
@@ -2534,8 +2535,8 @@ static void orient_shapes(const compeg_oriented_region *regions, size_t count, b
         (regions[r].orientation < 5u ? upright : transposed) = true;
 }
 
-Status compeg_decoder::pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_oriented_region *regions,
-                                            size_t count, const float *pad, void *dst, hipStream_t stream)
+Status compeg_decoder::pack_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
+                                     const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream)
 {
     CG_HIP(hipSetDevice(gpu->device));
     bool upright = false, transposed = false;
@@ -2556,15 +2557,16 @@ Status compeg_decoder::pack_tensor_oriented(const compeg_tensor_spec &spec, cons
         CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
     const void *records = nullptr;
     CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &records));
-    CG_HIP(launch_orient_tensor(records, tables_at, uint32_t(count), spec, filter, upright, transposed, pad, dst, stream));
+    CG_HIP(nhwc ? launch_nhwc_tensor(records, tables_at, uint32_t(count), spec, filter, *nhwc, upright, transposed, pad, dst, stream)
+                : launch_orient_tensor(records, tables_at, uint32_t(count), spec, filter, upright, transposed, pad, dst, stream));
     CG_HIP(hipEventRecord(decode_done, stream));
     decode_pending = true;
     last_stream = stream;
     return Status{};
 }
 
-Status compeg_batch::pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_oriented_region *regions,
-                                          size_t count, const float *pad, void *dst, hipStream_t stream)
+Status compeg_batch::pack_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
+                                   const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream)
 {
     CG_HIP(hipSetDevice(gpu->device));
     bool upright = false, transposed = false;
@@ -2589,10 +2591,35 @@ Status compeg_batch::pack_tensor_oriented(const compeg_tensor_spec &spec, const 
     }
     const void *device_records = nullptr;
     CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &device_records));
-    CG_HIP(launch_orient_tensor(device_records, tables_at, uint32_t(count), spec, filter, upright, transposed, pad, dst, stream));
+    CG_HIP(nhwc ? launch_nhwc_tensor(device_records, tables_at, uint32_t(count), spec, filter, *nhwc, upright, transposed, pad, dst, stream)
+                : launch_orient_tensor(device_records, tables_at, uint32_t(count), spec, filter, upright, transposed, pad, dst, stream));
     // (no timing events; the next decode on another stream records decode_done on last_stream, behind this)
     last_stream = stream;
     return Status{};
+}
+
+Status compeg_decoder::pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_oriented_region *regions,
+                                            size_t count, const float *pad, void *dst, hipStream_t stream)
+{
+    return pack_oriented(spec, filter, nullptr, regions, count, pad, dst, stream);
+}
+
+Status compeg_decoder::pack_tensor_nhwc(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec &nhwc,
+                                        const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream)
+{
+    return pack_oriented(spec, filter, &nhwc, regions, count, pad, dst, stream);
+}
+
+Status compeg_batch::pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_oriented_region *regions,
+                                          size_t count, const float *pad, void *dst, hipStream_t stream)
+{
+    return pack_oriented(spec, filter, nullptr, regions, count, pad, dst, stream);
+}
+
+Status compeg_batch::pack_tensor_nhwc(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec &nhwc,
+                                      const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream)
+{
+    return pack_oriented(spec, filter, &nhwc, regions, count, pad, dst, stream);
 }
 
 Status compeg_batch::pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream)

@@ -167,6 +167,12 @@ struct compeg_decoder {
     // its orientation 1..8 by now (checked by the caller, like everything else)
     compeg::Status pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_oriented_region *regions,
                                         size_t count, const float *pad, void *dst, hipStream_t stream);
+    // Channels-last tensor output: pack_tensor_oriented into [count][oh][ow][C]; nhwc checked by the caller.  Both go through
+    // pack_oriented (nhwc null: the planes)
+    compeg::Status pack_tensor_nhwc(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec &nhwc,
+                                    const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
+    compeg::Status pack_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
+                                 const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
     compeg::Status check_scan_result(bool &fell_back);
     compeg::Status preprocess_on_device(const compeg::ImageData &img, hipStream_t stream, uint32_t &nwords,
                                         uint32_t &nstarts, uint32_t &span, bool &fell_back, size_t blob_bytes,
@@ -278,5 +284,11 @@ struct compeg_batch {
     // its orientation 1..8 by now (checked by the caller, like everything else)
     compeg::Status pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_oriented_region *regions,
                                         size_t count, const float *pad, void *dst, hipStream_t stream);
+    // Channels-last tensor output: pack_tensor_oriented into [count][oh][ow][C]; nhwc checked by the caller.  Both go through
+    // pack_oriented (nhwc null: the planes)
+    compeg::Status pack_tensor_nhwc(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec &nhwc,
+                                    const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
+    compeg::Status pack_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
+                                 const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
     std::vector<uint32_t> orientations; // the EXIF orientation tag of every image of the last upload (note_batch_properties)
 };

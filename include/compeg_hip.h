@@ -612,6 +612,40 @@ int compeg_batch_pack_tensor_oriented(compeg_batch *batch, const compeg_tensor_s
                                       size_t count, const float *pad, void *device_dst, size_t dst_bytes,
                                       void *hip_stream);
 
+/* ---- Channels-last tensor output (extension) ---------------------------------
+ * compeg_*_pack_tensor_oriented into a channels-last destination of 3 or 4 channels: what torch.channels_last is for a
+ * model, and what PIL, OpenCV, an encoder or a viewer call HWC -- RGB or BGR pixels, or RGBA / RGBX with a constant
+ * fourth element -- without a second pass over the tensor.  New entry points beside the old ones: no existing call does
+ * anything different.
+ *
+ * Contract (exact).  Destination [count][oh][ow][C], tight, C = nhwc's channels, (ow, oh) = filter's out_width x
+ * out_height: the upright slot.  Element (s, y, x, c) for c < 3 is, bit for bit, element (s, c, y, x) of what
+ * compeg_*_pack_tensor_oriented stores for the same spec, filter, regions and pad; spec's order decides what c means, as
+ * it does for the planes.  For C = 4 element 3 of every pixel of every slot, the pad's pixels included, is `fill`
+ * converted to the element type as any value is (u8: rint and clamp; f16 / bf16: round to nearest even), with neither
+ * scale nor bias.  Every element of the tensor is written exactly once and no byte outside it is written.
+ * bytes_per_slot = oh * ow * C * element size; device_dst needs the element type's alignment only. */
+typedef struct compeg_nhwc_spec {
+    uint32_t channels;    /* 3 or 4 */
+    float fill;           /* channels == 4: the value of element 3 of every pixel (finite, whatever channels is) */
+    uint32_t reserved[2]; /* 0 */
+} compeg_nhwc_spec;       /* 16 bytes */
+/* No device needed: compeg_oriented_tensor_shape for the channels-last calls.  COMPEG_E_INVALID_ARG for what that one
+ * rejects, and for: nhwc NULL, channels other than 3 or 4, a fill that is not finite, a nonzero reserved word. */
+int compeg_nhwc_tensor_shape(const compeg_tensor_spec *spec, const compeg_filter_spec *filter, const compeg_nhwc_spec *nhwc,
+                             uint32_t width, uint32_t height, const compeg_oriented_region *region, uint32_t *pre_width,
+                             uint32_t *pre_height, size_t *bytes_per_slot);
+/* Like compeg_*_pack_tensor_oriented in everything they say about hip_stream, ordering, timing events, the decoder's
+ * texture, compeg_batch_wait, the copies made before the call returns, the messages and the rejections, with
+ * compeg_nhwc_tensor_shape's in place of compeg_oriented_tensor_shape's; nhwc is checked with the specs, before the
+ * object is looked at.  dst_bytes below count * bytes_per_slot: the message names both numbers. */
+int compeg_decoder_pack_tensor_nhwc(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
+                                    const compeg_nhwc_spec *nhwc, const compeg_oriented_region *regions, size_t count,
+                                    const float *pad, void *device_dst, size_t dst_bytes, void *hip_stream);
+int compeg_batch_pack_tensor_nhwc(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
+                                  const compeg_nhwc_spec *nhwc, const compeg_oriented_region *regions, size_t count,
+                                  const float *pad, void *device_dst, size_t dst_bytes, void *hip_stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

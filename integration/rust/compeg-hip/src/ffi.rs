@@ -85,6 +85,16 @@ pub struct compeg_oriented_region {
     pub reserved: u32,
 }
 
+/// The layout of `compeg_*_pack_tensor_nhwc` (compeg_hip.h, "Channels-last tensor output"): 3 or 4 channels a pixel,
+/// and the value of the fourth.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct compeg_nhwc_spec {
+    pub channels: u32,
+    pub fill: float,
+    pub reserved: [u32; 2],
+}
+
 pub const COMPEG_OK: c_int = 0;
 pub const COMPEG_E_INVALID_ARG: c_int = -1;
 pub const COMPEG_E_UNSUPPORTED: c_int = -2;
@@ -276,4 +286,17 @@ extern "C" {
                                              filter: *const compeg_filter_spec, regions: *const compeg_oriented_region,
                                              count: usize, pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
                                              hip_stream: *mut c_void) -> c_int;
+
+    // Channels-last tensor output (extension)
+    pub fn compeg_nhwc_tensor_shape(spec: *const compeg_tensor_spec, filter: *const compeg_filter_spec, nhwc: *const compeg_nhwc_spec,
+                                    width: u32, height: u32, region: *const compeg_oriented_region, pre_width: *mut u32,
+                                    pre_height: *mut u32, bytes_per_slot: *mut usize) -> c_int;
+    pub fn compeg_decoder_pack_tensor_nhwc(dec: *mut compeg_decoder, spec: *const compeg_tensor_spec, filter: *const compeg_filter_spec,
+                                           nhwc: *const compeg_nhwc_spec, regions: *const compeg_oriented_region, count: usize,
+                                           pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
+                                           hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_batch_pack_tensor_nhwc(batch: *mut compeg_batch, spec: *const compeg_tensor_spec, filter: *const compeg_filter_spec,
+                                         nhwc: *const compeg_nhwc_spec, regions: *const compeg_oriented_region, count: usize,
+                                         pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
+                                         hip_stream: *mut c_void) -> c_int;
 }

@@ -309,6 +309,34 @@ impl OrientedRegion {
     }
 }
 
+/// The layout of `Decoder::pack_tensor_nhwc` / `Batch::pack_tensor_nhwc` (compeg_hip.h, "Channels-last tensor output"):
+/// the destination is `[count][oh][ow][channels]`; with four channels element 3 of every pixel is `fill`.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub enum NhwcSpec {
+    /// Three elements a pixel, in the tensor spec's order.
+    Three,
+    /// Four: the fourth is this value, converted to the element type like any other, with neither scale nor bias.
+    Four { fill: f32 },
+}
+
+impl NhwcSpec {
+    fn raw(&self) -> ffi::compeg_nhwc_spec {
+        match *self {
+            NhwcSpec::Three => ffi::compeg_nhwc_spec { channels: 3, fill: 0.0, reserved: [0; 2] },
+            NhwcSpec::Four { fill } => ffi::compeg_nhwc_spec { channels: 4, fill, reserved: [0; 2] },
+        }
+    }
+
+    /// `(pre_width, pre_height, bytes)`: `OrientedRegion::shape` for the channels-last calls.  No device needed.
+    pub fn shape(&self, tensor: &TensorSpec, filter: &FilterSpec, width: u32, height: u32, region: &OrientedRegion) -> Result<(u32, u32, usize)> {
+        let (mut w, mut h, mut n) = (0, 0, 0);
+        check(unsafe {
+            ffi::compeg_nhwc_tensor_shape(&tensor.raw(), &filter.raw(), &self.raw(), width, height, &region.raw(), &mut w, &mut h, &mut n)
+        })?;
+        Ok((w, h, n))
+    }
+}
+
 /// Device + stream + loaded gfx950 code object.  Immutable after creation and
 /// reference-counted inside the library; share it as `Arc<Gpu>` like the reference.
 pub struct Gpu {
@@ -605,6 +633,18 @@ impl Decoder {
                                                        dst_bytes, stream.0))
     }
 
+    /// Extension: `pack_tensor_oriented` into a channels-last destination, `[count][oh][ow][C]`.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn pack_tensor_nhwc(&mut self, spec: &TensorSpec, filter: &FilterSpec, nhwc: &NhwcSpec, regions: &[OrientedRegion],
+                                   pad: Option<&[f32; 3]>, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        let raw: Vec<ffi::compeg_oriented_region> = regions.iter().map(OrientedRegion::raw).collect();
+        let pad = pad.map_or(ptr::null(), |p| p.as_ptr());
+        check(ffi::compeg_decoder_pack_tensor_nhwc(self.raw.as_ptr(), &spec.raw(), &filter.raw(), &nhwc.raw(), raw.as_ptr(), raw.len(), pad,
+                                                   device_dst, dst_bytes, stream.0))
+    }
+
     /// Test helper (the reference's tests copy the texture to a buffer): waits and
     /// returns the image's `width x height` corner, tightly packed.
     pub fn read_output(&mut self, width: u32, height: u32) -> Result<Vec<u8>> {
@@ -818,6 +858,19 @@ impl Batch {
         let pad = pad.map_or(ptr::null(), |p| p.as_ptr());
         check(ffi::compeg_batch_pack_tensor_oriented(self.raw.as_ptr(), &spec.raw(), &filter.raw(), raw.as_ptr(), raw.len(), pad, device_dst,
                                                      dst_bytes, stream.0))
+    }
+
+    /// Records on `stream` the channels-last pack of the last decode: `pack_tensor_oriented` into `[count][oh][ow][C]`.
+    /// `wait` covers it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn pack_tensor_nhwc(&mut self, spec: &TensorSpec, filter: &FilterSpec, nhwc: &NhwcSpec, regions: &[OrientedRegion],
+                                   pad: Option<&[f32; 3]>, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        let raw: Vec<ffi::compeg_oriented_region> = regions.iter().map(OrientedRegion::raw).collect();
+        let pad = pad.map_or(ptr::null(), |p| p.as_ptr());
+        check(ffi::compeg_batch_pack_tensor_nhwc(self.raw.as_ptr(), &spec.raw(), &filter.raw(), &nhwc.raw(), raw.as_ptr(), raw.len(), pad,
+                                                 device_dst, dst_bytes, stream.0))
     }
 
     /// The EXIF orientation tag (1..8) of image `index` of the last upload.

@@ -32,6 +32,11 @@ The oriented arm (--oriented; default table profiles/tensor_oriented.txt), the s
 whole frames -> 224x224, bicubic, k = 1, at the orientations 1, 2 and 6, beside Batch.pack_tensor_filtered and the chains
 a user writes without it: the filtered pack into a temporary, then torch.rot90(t, -1, (2, 3)).contiguous() for
 orientation 6, t.flip(3) for orientation 2.
+
+The channels-last arm (--nhwc; default table profiles/tensor_nhwc.txt), the same method: Batch.pack_tensor_nhwc with 3 and
+with 4 channels beside the planar Batch.pack_tensor_oriented and the chain a user writes without it -- the planar pack into
+a temporary, then .contiguous(memory_format=torch.channels_last) --, to 224x224 and, where the stores are not small beside
+the loads, 1080p -> 1920x1080 without a resize.
 """
 import argparse
 import os
@@ -394,6 +399,79 @@ def oriented_arm(args, torch, compeg_amd, images_of, resident, gpu, stream):
     return "\n".join(lines) + "\n"
 
 
+# the channels-last arm: (name, (width, height), (ow, oh), kernel, element type, orientation)
+NHWC_CONFIGS = (("1080p -> 224x224 bicubic f16 o=1", (1920, 1080), (224, 224), "bicubic", "f16", 1),
+                ("1080p -> 224x224 bicubic f16 o=6", (1920, 1080), (224, 224), "bicubic", "f16", 6),
+                ("4K -> 224x224 bicubic f16 o=1", (3840, 2160), (224, 224), "bicubic", "f16", 1),
+                ("4K -> 224x224 bicubic f16 o=6", (3840, 2160), (224, 224), "bicubic", "f16", 6),
+                ("1080p -> 224x224 bicubic u8 o=6", (1920, 1080), (224, 224), "bicubic", "u8", 6),
+                ("1080p -> 224x224 bicubic f32 o=6", (1920, 1080), (224, 224), "bicubic", "f32", 6),
+                ("1080p -> 1920x1080 triangle u8 o=1", (1920, 1080), (1920, 1080), "triangle", "u8", 1))   # no resize: the stores are not small
+
+
+def nhwc_arm(args, torch, compeg_amd, images_of, resident, gpu, stream):
+    """The table of the channels-last arm, as text."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import nhwc_reference as nr   # the header's contract in numpy
+    n, handle = args.batch, stream.cuda_stream
+    torch_type = {"u8": torch.uint8, "f16": torch.float16, "f32": torch.float32}
+    lines = [f"channels-last tensor output: {n} resident 4:2:2 DRI=4 frames per configuration, decoded once; {gpu.name()}; library {os.path.relpath(compeg_amd.LIB_PATH, ROOT)}",
+             "planar = Batch.pack_tensor_oriented of whole frames into [N, 3, oh, ow]; nhwc3 / nhwc4 = Batch.pack_tensor_nhwc of the same regions into "
+             "[N, oh, ow, 3] / [N, oh, ow, 4] (fill 255 for u8, 1 otherwise); chain = the planar pack into a temporary, then "
+             ".contiguous(memory_format=torch.channels_last)",
+             f"HIP events on one stream, the arms of a configuration launch by launch in turn, their order turning round from one repetition to the "
+             f"next, one untimed round in front; median of {args.reps} (min .. max), ms"]
+    verdicts = []
+    keys = ["planar", "nhwc3", "nhwc4", "chain"]
+    for name, (w, h), (ow, oh), kernel, dtype, o in NHWC_CONFIGS:
+        items = images_of(w, h)
+        batch = resident([items[i % len(items)] for i in range(n)])
+        whole = [(i, None, None) for i in range(n)]
+        scale = [1.0] * 3 if dtype == "u8" else [1.0 / (255.0 * s) for s in STD]
+        bias = [0.0] * 3 if dtype == "u8" else [-m / s for m, s in zip(MEAN, STD)]
+        fill = 255.0 if dtype == "u8" else 1.0
+        kw = dict(orientation=o, kernel=kernel, dtype=dtype, scale=scale, bias=bias, hip_stream=handle)
+        out = {key: torch.empty((n, 3, oh, ow), dtype=torch_type[dtype], device="cuda") for key in ("planar", "tmp")}
+        out["nhwc3"] = torch.empty((n, oh, ow, 3), dtype=torch_type[dtype], device="cuda")
+        out["nhwc4"] = torch.empty((n, oh, ow, 4), dtype=torch_type[dtype], device="cuda")
+
+        def primer():
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < PRIME_SECONDS:
+                batch.decode(handle)
+                batch.wait()
+
+        def chain():
+            batch.pack_tensor_oriented(out["tmp"], (ow, oh), whole, **kw)
+            out["chain"] = out["tmp"].contiguous(memory_format=torch.channels_last)
+
+        arms = [lambda: batch.pack_tensor_oriented(out["planar"], (ow, oh), whole, **kw),
+                lambda: batch.pack_tensor_nhwc(out["nhwc3"], (ow, oh), whole, channels=3, **kw),
+                lambda: batch.pack_tensor_nhwc(out["nhwc4"], (ow, oh), whole, channels=4, fill=fill, **kw), chain]
+        t = dict(zip(keys, _timed_in_turn(torch, stream, args.reps, primer, arms)))
+        planar = nr.orf.expected(batch.read_output(0), (ow, oh), 1, dtype, scale, bias, "rgb", kernel, o=o)
+        wrong = {"planar": int((planar != out["planar"][0].cpu().numpy()).sum()),
+                 "nhwc3": int((nr.channels_last(planar) != out["nhwc3"][0].cpu().numpy()).sum()),
+                 "nhwc4": int((nr.channels_last(planar, 4, fill, dtype) != out["nhwc4"][0].cpu().numpy()).sum())}
+        lines += ["", name]
+        for key in keys:
+            note = (f"   slot 0: {wrong[key]} elements off the contract" if key != "chain" else
+                    f"   all slots equal to nhwc3: {bool(torch.equal(out['chain'].permute(0, 2, 3, 1), out['nhwc3']))}")
+            lines.append(f"  {key:<8} {_cell(t[key])}{note}")
+        for key in ("nhwc3", "nhwc4"):
+            for other in ("chain", "planar"):
+                a, b = t[key], t[other]
+                ratio = statistics.median(a) / statistics.median(b)
+                verdict = ("faster" if statistics.median(a) < statistics.median(b) else "slower") if _gap(a, b) else "within the rows' own spread"
+                lines.append(f"  {key} against {other}: {ratio:.2f}, {verdict}")
+                verdicts.append(f"{name}: {key}/{other} {ratio:.2f} ({verdict})")
+        print("\n".join(lines[-(len(keys) + 5):]), file=sys.stderr, flush=True)   # (progress: the table itself is printed at the end)
+        del out, batch
+        torch.cuda.empty_cache()
+    lines += [""] + verdicts
+    return "\n".join(lines) + "\n"
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=256)
@@ -405,9 +483,10 @@ def main():
     p.add_argument("--regions", action="store_true", help="the regions arm (Batch.pack_tensor_regions) instead; default table profiles/tensor_regions.txt")
     p.add_argument("--filtered", action="store_true", help="the filtered arm (Batch.pack_tensor_filtered) instead; default table profiles/tensor_filtered.txt")
     p.add_argument("--oriented", action="store_true", help="the oriented arm (Batch.pack_tensor_oriented) instead; default table profiles/tensor_oriented.txt")
+    p.add_argument("--nhwc", action="store_true", help="the channels-last arm (Batch.pack_tensor_nhwc) instead; default table profiles/tensor_nhwc.txt")
     args = p.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "tensor_oriented.txt" if args.oriented else "tensor_filtered.txt" if args.filtered else "tensor_regions.txt" if args.regions else
+        args.out = os.path.join(ROOT, "profiles", "tensor_nhwc.txt" if args.nhwc else "tensor_oriented.txt" if args.oriented else "tensor_filtered.txt" if args.filtered else "tensor_regions.txt" if args.regions else
                                 "tensor_resize_antialias.txt" if args.antialias else "tensor_resize.txt")
 
     import torch
@@ -440,8 +519,9 @@ def main():
         batch.wait()
         return batch
 
-    if args.antialias or args.regions or args.filtered or args.oriented:
-        text = (oriented_arm(args, torch, compeg_amd, images_of, resident, gpu, stream) if args.oriented else
+    if args.antialias or args.regions or args.filtered or args.oriented or args.nhwc:
+        text = (nhwc_arm(args, torch, compeg_amd, images_of, resident, gpu, stream) if args.nhwc else
+                oriented_arm(args, torch, compeg_amd, images_of, resident, gpu, stream) if args.oriented else
                 filtered_arm(args, torch, compeg_amd, images_of, resident, gpu, stream) if args.filtered else
                 regions_arm(args, torch, F, compeg_amd, images_of, resident, gpu, stream) if args.regions else
                 antialias_arm(args, torch, compeg_amd, images_of, resident, gpu, stream))
