@@ -246,15 +246,9 @@ int check_region(const compeg_region *region, const compeg_tensor_spec *spec, co
     return COMPEG_OK;
 }
 
-// What both region packs check before they look at their object: the specs, the list, the pad.
-int check_region_call(const compeg_tensor_spec *spec, const compeg_resize_spec *resize, const compeg_region *regions, size_t count,
-                      const float *pad, size_t *elem_bytes)
+// What every slot pack checks, behind its specs, before it looks at its object: the list and the pad.
+int check_slot_list(const void *regions, size_t count, const float *pad)
 {
-    int rc = check_tensor_spec(spec, elem_bytes);
-    if (rc == COMPEG_OK)
-        rc = check_resize_spec(resize);
-    if (rc != COMPEG_OK)
-        return rc;
     if (!regions)
         return fail(COMPEG_E_INVALID_ARG, "tensor: regions is NULL");
     if (count == 0)
@@ -263,16 +257,6 @@ int check_region_call(const compeg_tensor_spec *spec, const compeg_resize_spec *
         if (!std::isfinite(pad[c]))
             return fail(COMPEG_E_INVALID_ARG, ("tensor: pad of channel " + std::to_string(c) + " is not finite").c_str());
     return COMPEG_OK;
-}
-
-// Bytes of `count` slots, or false where size_t does not hold them.
-bool region_tensor_bytes(const compeg_resize_spec *resize, size_t elem, size_t count, size_t *bytes)
-{
-    const size_t slot = size_t(3) * size_t(resize->out_height) * size_t(resize->out_width) * elem;
-    if (count > SIZE_MAX / slot)
-        return false;
-    *bytes = slot * count;
-    return true;
 }
 
 // compeg_filter_spec as the header has it.  (The texts name values, not the header's macros.)
@@ -369,33 +353,222 @@ int check_nhwc_spec(const compeg_nhwc_spec *nhwc)
     return COMPEG_OK;
 }
 
-// The bytes of `count` slots of `channels` elements a pixel at the filter's output extent; false: size_t does not hold them.
-bool slot_tensor_bytes(const compeg_filter_spec *filter, size_t channels, size_t elem, size_t count, size_t *bytes)
+// What the *_tensor_shape calls end with: the prefiltered extent of the checked source rectangle and a slot's bytes.
+int shape_result(const compeg_rect &src, uint32_t k, size_t slot_bytes, uint32_t *pre_width, uint32_t *pre_height, size_t *bytes)
 {
-    const size_t slot = channels * size_t(filter->out_height) * size_t(filter->out_width) * elem;
-    if (count > SIZE_MAX / slot)
+    if (pre_width)
+        *pre_width = src.width / k;
+    if (pre_height)
+        *pre_height = src.height / k;
+    if (bytes)
+        *bytes = slot_bytes;
+    return ok();
+}
+
+// What the pack calls ask of their object, a decoder (one image, its last: image 0) or a batch.
+const char *null_text(const compeg_decoder *) { return "dec is NULL"; }
+const char *null_text(const compeg_batch *) { return "batch is NULL"; }
+
+bool output_decoded(const compeg_decoder &dec) { return dec.have_last && dec.out.ptr; }
+bool output_decoded(const compeg_batch &batch) { return batch.count && batch.output_decoded; }
+
+template <class Owner>
+int check_decoded(const Owner &owner)
+{
+    return output_decoded(owner) ? COMPEG_OK : fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
+}
+
+template <class Owner>
+hipStream_t stream_of(const Owner &owner, void *hip_stream)
+{
+    return hip_stream ? static_cast<hipStream_t>(hip_stream) : owner.gpu->stream;
+}
+
+// The orientation tag of image i, whatever i is (1 beyond the images: the index is refused where the list is checked)
+uint32_t image_tag(const compeg_decoder &dec, uint32_t) { return dec.last_orientation; }
+uint32_t image_tag(const compeg_batch &batch, uint32_t i) { return i < batch.orientations.size() ? batch.orientations[i] : 1u; }
+
+// ... and its extent; false with what is wrong with i.  (The texture never shrinks: the last image's own extent.)
+bool image_extent(const compeg_decoder &dec, uint32_t i, uint32_t *width, uint32_t *height, std::string *why)
+{
+    if (i != 0u) {
+        *why = "image " + std::to_string(i) + ", a decoder has image 0 only";
         return false;
-    *bytes = slot * count;
+    }
+    *width = dec.last_w;
+    *height = dec.last_h;
     return true;
 }
 
-// What both filtered packs check before they look at their object: the specs, the list, the pad.
-int check_filtered_call(const compeg_tensor_spec *spec, const compeg_filter_spec *filter, const compeg_region *regions, size_t count,
-                        const float *pad, size_t *elem_bytes)
+bool image_extent(const compeg_batch &batch, uint32_t i, uint32_t *width, uint32_t *height, std::string *why)
 {
-    int rc = check_tensor_spec(spec, elem_bytes);
-    if (rc == COMPEG_OK)
-        rc = check_filter_spec(filter);
-    if (rc != COMPEG_OK)
-        return rc;
-    if (!regions)
-        return fail(COMPEG_E_INVALID_ARG, "tensor: regions is NULL");
-    if (count == 0)
-        return fail(COMPEG_E_INVALID_ARG, "tensor: a region count of 0");
-    for (int c = 0; pad && c < 3; c++)
-        if (!std::isfinite(pad[c]))
-            return fail(COMPEG_E_INVALID_ARG, ("tensor: pad of channel " + std::to_string(c) + " is not finite").c_str());
-    return COMPEG_OK;
+    if (i >= batch.count) {
+        *why = "image " + std::to_string(i) + " is beyond the batch's " + std::to_string(batch.count) + " images";
+        return false;
+    }
+    *width = batch.descs[i].out_w;
+    *height = batch.descs[i].out_h;
+    return true;
+}
+
+struct SlotImage {
+    uint32_t width, height, orientation; // the image a region names: its stored extent and its tag
+};
+
+const compeg_region &plain(const compeg_region &region) { return region; }
+const compeg_region &plain(const compeg_oriented_region &region) { return region.region; }
+
+// What a slot family -- region, filtered, oriented or channels-last tensor output -- adds to the two roads below: its
+// specs (the layout's on its own: a pack checks it behind the list), a slot's elements, its grid, its check of one
+// region and its pack.
+struct RegionPack {
+    using Region = compeg_region;
+    const compeg_tensor_spec *spec;
+    const compeg_resize_spec *resize;
+    int check_specs(size_t *elem_bytes) const
+    {
+        const int rc = check_tensor_spec(spec, elem_bytes);
+        return rc == COMPEG_OK ? check_resize_spec(resize) : rc;
+    }
+    int check_layout() const { return COMPEG_OK; }
+    size_t slot_elements() const { return size_t(3) * size_t(resize->out_height) * size_t(resize->out_width); }
+    template <class Owner>
+    bool grid_fits(const Owner &, const Region *, size_t count) const { return compeg::region_grid_fits(uint32_t(count), *spec, *resize); }
+    int check_one(const Region *region, const SlotImage &image, const std::string &which, Region *out) const
+    {
+        return check_region(region, spec, resize, image.width, image.height, which, out);
+    }
+    template <class Owner>
+    Status pack(Owner &owner, const Region *list, size_t count, const float *pad, void *dst, hipStream_t stream) const
+    {
+        return owner.pack_tensor_regions(*spec, *resize, list, count, pad, dst, stream);
+    }
+};
+
+struct FilterPack {
+    using Region = compeg_region;
+    const compeg_tensor_spec *spec;
+    const compeg_filter_spec *filter;
+    int check_specs(size_t *elem_bytes) const
+    {
+        const int rc = check_tensor_spec(spec, elem_bytes);
+        return rc == COMPEG_OK ? check_filter_spec(filter) : rc;
+    }
+    int check_layout() const { return COMPEG_OK; }
+    size_t slot_elements() const { return size_t(3) * size_t(filter->out_height) * size_t(filter->out_width); }
+    template <class Owner>
+    bool grid_fits(const Owner &, const Region *, size_t count) const { return compeg::filter_grid_fits(uint32_t(count), *spec, *filter); }
+    int check_one(const Region *region, const SlotImage &image, const std::string &which, Region *out) const
+    {
+        return check_filtered_region(region, spec, filter, image.width, image.height, which, out);
+    }
+    template <class Owner>
+    Status pack(Owner &owner, const Region *list, size_t count, const float *pad, void *dst, hipStream_t stream) const
+    {
+        return owner.pack_tensor_filtered(*spec, *filter, list, count, pad, dst, stream);
+    }
+};
+
+// Oriented (channels_last false: nhwc is not looked at) and channels-last tensor output (true: nhwc as the caller gave
+// it, NULL included): one family, so that the two check the same things in the same order.
+struct OrientPack {
+    using Region = compeg_oriented_region;
+    const compeg_tensor_spec *spec;
+    const compeg_filter_spec *filter;
+    bool channels_last;
+    const compeg_nhwc_spec *nhwc;
+    int check_specs(size_t *elem_bytes) const { return FilterPack{spec, filter}.check_specs(elem_bytes); }
+    int check_layout() const { return channels_last ? check_nhwc_spec(nhwc) : COMPEG_OK; }
+    size_t slot_elements() const { return size_t(filter->out_height) * size_t(filter->out_width) * size_t(channels_last ? nhwc->channels : 3u); }
+    // (which slot shapes the list needs takes the orientations alone; one above 8 is the list's check to name, an image
+    // beyond the object's too)
+    template <class Owner>
+    bool grid_fits(const Owner &owner, const Region *regions, size_t count) const
+    {
+        bool upright = false, transposed = false;
+        for (size_t r = 0; r < count; r++) {
+            const uint32_t o = regions[r].orientation == COMPEG_ORIENT_FROM_IMAGE ? image_tag(owner, regions[r].region.image) : regions[r].orientation;
+            (o < 5u ? upright : transposed) = true;
+        }
+        return compeg::orient_grid_fits(uint32_t(count), *spec, *filter, upright, transposed);
+    }
+    // (src as a whole rectangle, dst as dst', the orientation 1..8)
+    int check_one(const Region *region, const SlotImage &image, const std::string &which, Region *out) const
+    {
+        return check_oriented_region(region, spec, filter, image.width, image.height, image.orientation, which, out);
+    }
+    template <class Owner>
+    Status pack(Owner &owner, const Region *list, size_t count, const float *pad, void *dst, hipStream_t stream) const
+    {
+        return owner.pack_tensor_oriented(*spec, *filter, channels_last ? nhwc : nullptr, list, count, pad, dst, stream);
+    }
+};
+
+// compeg_{region,filtered,oriented,nhwc}_tensor_shape: the family's specs and its check of one region of a width x height
+// image that carries no tag; then the prefiltered extent of the region's source and a slot's bytes.
+template <class Family>
+int slot_tensor_shape(const Family &family, const typename Family::Region *region, uint32_t width, uint32_t height, uint32_t *pre_width,
+                      uint32_t *pre_height, size_t *bytes_per_slot)
+{
+    return guarded([&] {
+        size_t elem = 0;
+        int rc = family.check_specs(&elem);
+        if (rc == COMPEG_OK)
+            rc = family.check_layout();
+        typename Family::Region r{};
+        if (rc == COMPEG_OK)
+            rc = family.check_one(region, SlotImage{width, height, 1u}, "", &r);
+        if (rc != COMPEG_OK)
+            return rc;
+        return shape_result(plain(r).src, family.spec->downscale, family.slot_elements() * elem, pre_width, pre_height, bytes_per_slot);
+    });
+}
+
+// Every slot pack call, of either object: what does not depend on the object first (it is checked where no device
+// is), the launch's limits and the destination before the list is copied (nothing is allocated for a count no call
+// takes), then the copy of the caller's list, every region checked and resolved to whole rectangles.
+template <class Owner, class Family>
+int pack_slot_tensor(Owner *owner, const Family &family, const typename Family::Region *regions, size_t count, const float *pad,
+                     void *device_dst, size_t dst_bytes, void *hip_stream)
+{
+    return guarded([&] {
+        size_t elem = 0;
+        int rc = family.check_specs(&elem);
+        if (rc == COMPEG_OK)
+            rc = check_slot_list(regions, count, pad);
+        if (rc == COMPEG_OK)
+            rc = family.check_layout();
+        if (rc != COMPEG_OK)
+            return rc;
+        if (!owner)
+            return fail(COMPEG_E_INVALID_ARG, null_text(owner));
+        rc = check_decoded(*owner);
+        if (rc != COMPEG_OK)
+            return rc;
+        const size_t slot = family.slot_elements() * elem;
+        if (count > SIZE_MAX / slot)
+            return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
+        if (count > 0xffffffffull || !family.grid_fits(*owner, regions, count))
+            return fail(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
+        rc = check_tensor_destination(device_dst, dst_bytes, slot * count, elem);
+        if (rc != COMPEG_OK)
+            return rc;
+        std::vector<typename Family::Region> list(count);
+        for (size_t r = 0; r < count; r++) {
+            const std::string which = "region " + std::to_string(r) + ": ";
+            const uint32_t i = plain(regions[r]).image;
+            SlotImage image{0u, 0u, image_tag(*owner, i)};
+            std::string why;
+            if (!image_extent(*owner, i, &image.width, &image.height, &why))
+                return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + why).c_str());
+            rc = family.check_one(regions + r, image, which, &list[r]);
+            if (rc != COMPEG_OK)
+                return rc;
+        }
+        const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
+        Status s = family.pack(*owner, list.data(), count, pad_copy, device_dst, stream_of(*owner, hip_stream));
+        return s.ok() ? ok() : fail(s);
+    });
 }
 
 } // namespace
@@ -1246,13 +1419,13 @@ int compeg_decoder_pack_tensor(compeg_decoder *dec, const compeg_tensor_spec *sp
 {
     return guarded([&] {
         if (!dec)
-            return fail(COMPEG_E_INVALID_ARG, "dec is NULL");
+            return fail(COMPEG_E_INVALID_ARG, null_text(dec));
         size_t elem = 0;
         int rc = check_tensor_spec(spec, &elem);
+        if (rc == COMPEG_OK)
+            rc = check_decoded(*dec);
         if (rc != COMPEG_OK)
             return rc;
-        if (!dec->have_last || !dec->out.ptr)
-            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
         // (the texture never shrinks: the last image's own extent, at the allocation's pitch)
         uint32_t ow = 0, oh = 0;
         size_t bytes = 0;
@@ -1261,7 +1434,7 @@ int compeg_decoder_pack_tensor(compeg_decoder *dec, const compeg_tensor_spec *sp
             rc = check_tensor_destination(device_dst, dst_bytes, bytes, elem);
         if (rc != COMPEG_OK)
             return rc;
-        Status s = dec->pack_tensor(*spec, device_dst, hip_stream ? static_cast<hipStream_t>(hip_stream) : dec->gpu->stream);
+        Status s = dec->pack_tensor(*spec, device_dst, stream_of(*dec, hip_stream));
         return s.ok() ? ok() : fail(s);
     });
 }
@@ -1271,13 +1444,13 @@ int compeg_batch_pack_tensor(compeg_batch *batch, const compeg_tensor_spec *spec
 {
     return guarded([&] {
         if (!batch)
-            return fail(COMPEG_E_INVALID_ARG, "batch is NULL");
+            return fail(COMPEG_E_INVALID_ARG, null_text(batch));
         size_t elem = 0;
         int rc = check_tensor_spec(spec, &elem);
+        if (rc == COMPEG_OK)
+            rc = check_decoded(*batch);
         if (rc != COMPEG_OK)
             return rc;
-        if (!batch->count || !batch->output_decoded)
-            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
         const ImageDesc &first = batch->descs[0];
         for (size_t i = 1; i < batch->count; i++)
             if (batch->descs[i].out_w != first.out_w || batch->descs[i].out_h != first.out_h)
@@ -1291,7 +1464,7 @@ int compeg_batch_pack_tensor(compeg_batch *batch, const compeg_tensor_spec *spec
             rc = check_tensor_destination(device_dst, dst_bytes, bytes * batch->count, elem);
         if (rc != COMPEG_OK)
             return rc;
-        Status s = batch->pack_tensor(*spec, device_dst, hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream);
+        Status s = batch->pack_tensor(*spec, device_dst, stream_of(*batch, hip_stream));
         return s.ok() ? ok() : fail(s);
     });
 }
@@ -1313,13 +1486,8 @@ int compeg_resized_tensor_shape(const compeg_tensor_spec *spec, const compeg_res
             rc = check_antialias_ratio(resize, r, spec->downscale, "");
         if (rc != COMPEG_OK)
             return rc;
-        if (pre_width)
-            *pre_width = r.width / spec->downscale;
-        if (pre_height)
-            *pre_height = r.height / spec->downscale;
-        if (bytes_per_image)
-            *bytes_per_image = size_t(3) * size_t(resize->out_height) * size_t(resize->out_width) * elem;
-        return ok();
+        return shape_result(r, spec->downscale, size_t(3) * size_t(resize->out_height) * size_t(resize->out_width) * elem, pre_width, pre_height,
+                            bytes_per_image);
     });
 }
 
@@ -1328,15 +1496,15 @@ int compeg_decoder_pack_tensor_resized(compeg_decoder *dec, const compeg_tensor_
 {
     return guarded([&] {
         if (!dec)
-            return fail(COMPEG_E_INVALID_ARG, "dec is NULL");
+            return fail(COMPEG_E_INVALID_ARG, null_text(dec));
         size_t elem = 0;
         int rc = check_tensor_spec(spec, &elem);
         if (rc == COMPEG_OK)
             rc = check_resize_spec(resize);
+        if (rc == COMPEG_OK)
+            rc = check_decoded(*dec);
         if (rc != COMPEG_OK)
             return rc;
-        if (!dec->have_last || !dec->out.ptr)
-            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
         // (the texture never shrinks: the last image's own extent, at the allocation's pitch)
         compeg_rect r{};
         rc = check_crop(crop, dec->last_w, dec->last_h, spec->downscale, "", &r);
@@ -1346,7 +1514,7 @@ int compeg_decoder_pack_tensor_resized(compeg_decoder *dec, const compeg_tensor_
             rc = check_tensor_destination(device_dst, dst_bytes, size_t(3) * size_t(resize->out_height) * size_t(resize->out_width) * elem, elem);
         if (rc != COMPEG_OK)
             return rc;
-        Status s = dec->pack_tensor_resized(*spec, *resize, r, device_dst, hip_stream ? static_cast<hipStream_t>(hip_stream) : dec->gpu->stream);
+        Status s = dec->pack_tensor_resized(*spec, *resize, r, device_dst, stream_of(*dec, hip_stream));
         return s.ok() ? ok() : fail(s);
     });
 }
@@ -1356,15 +1524,15 @@ int compeg_batch_pack_tensor_resized(compeg_batch *batch, const compeg_tensor_sp
 {
     return guarded([&] {
         if (!batch)
-            return fail(COMPEG_E_INVALID_ARG, "batch is NULL");
+            return fail(COMPEG_E_INVALID_ARG, null_text(batch));
         size_t elem = 0;
         int rc = check_tensor_spec(spec, &elem);
         if (rc == COMPEG_OK)
             rc = check_resize_spec(resize);
+        if (rc == COMPEG_OK)
+            rc = check_decoded(*batch);
         if (rc != COMPEG_OK)
             return rc;
-        if (!batch->count || !batch->output_decoded)
-            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
         std::vector<compeg_rect> rects(batch->count);
         for (size_t i = 0; i < batch->count; i++) {
             rc = check_crop(crops ? crops + i : nullptr, batch->descs[i].out_w, batch->descs[i].out_h, spec->downscale,
@@ -1377,7 +1545,7 @@ int compeg_batch_pack_tensor_resized(compeg_batch *batch, const compeg_tensor_sp
         rc = check_tensor_destination(device_dst, dst_bytes, size_t(3) * size_t(resize->out_height) * size_t(resize->out_width) * elem * batch->count, elem);
         if (rc != COMPEG_OK)
             return rc;
-        Status s = batch->pack_tensor_resized(*spec, *resize, rects.data(), device_dst, hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream);
+        Status s = batch->pack_tensor_resized(*spec, *resize, rects.data(), device_dst, stream_of(*batch, hip_stream));
         return s.ok() ? ok() : fail(s);
     });
 }
@@ -1418,103 +1586,21 @@ int compeg_region_fit(uint32_t src_width, uint32_t src_height, uint32_t out_widt
 int compeg_region_tensor_shape(const compeg_tensor_spec *spec, const compeg_resize_spec *resize, uint32_t width, uint32_t height,
                                const compeg_region *region, uint32_t *pre_width, uint32_t *pre_height, size_t *bytes_per_slot)
 {
-    return guarded([&] {
-        size_t elem = 0;
-        int rc = check_tensor_spec(spec, &elem);
-        if (rc == COMPEG_OK)
-            rc = check_resize_spec(resize);
-        compeg_region r{};
-        if (rc == COMPEG_OK)
-            rc = check_region(region, spec, resize, width, height, "", &r);
-        if (rc != COMPEG_OK)
-            return rc;
-        if (pre_width)
-            *pre_width = r.src.width / spec->downscale;
-        if (pre_height)
-            *pre_height = r.src.height / spec->downscale;
-        if (bytes_per_slot)
-            *bytes_per_slot = size_t(3) * size_t(resize->out_height) * size_t(resize->out_width) * elem;
-        return ok();
-    });
+    return slot_tensor_shape(RegionPack{spec, resize}, region, width, height, pre_width, pre_height, bytes_per_slot);
 }
 
 int compeg_decoder_pack_tensor_regions(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_resize_spec *resize,
                                        const compeg_region *regions, size_t count, const float *pad, void *device_dst, size_t dst_bytes,
                                        void *hip_stream)
 {
-    return guarded([&] {
-        // (what does not depend on the object first: it is checked where no device is)
-        size_t elem = 0, bytes = 0;
-        int rc = check_region_call(spec, resize, regions, count, pad, &elem);
-        if (rc != COMPEG_OK)
-            return rc;
-        if (!dec)
-            return fail(COMPEG_E_INVALID_ARG, "dec is NULL");
-        if (!dec->have_last || !dec->out.ptr)
-            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
-        if (!region_tensor_bytes(resize, elem, count, &bytes))
-            return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
-        // (the launch's limits and the destination before the list is copied: nothing is allocated for a count no call takes)
-        if (count > 0xffffffffull || !compeg::region_grid_fits(uint32_t(count), *spec, *resize))
-            return fail(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
-        rc = check_tensor_destination(device_dst, dst_bytes, bytes, elem);
-        if (rc != COMPEG_OK)
-            return rc;
-        // (the copy of the caller's list: src and dst as whole rectangles)
-        std::vector<compeg_region> list(count);
-        for (size_t r = 0; r < count; r++) {
-            const std::string which = "region " + std::to_string(r) + ": ";
-            if (regions[r].image != 0u)
-                return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "image " + std::to_string(regions[r].image) + ", a decoder has image 0 only").c_str());
-            rc = check_region(regions + r, spec, resize, dec->last_w, dec->last_h, which, &list[r]);
-            if (rc != COMPEG_OK)
-                return rc;
-        }
-        const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
-        Status s = dec->pack_tensor_regions(*spec, *resize, list.data(), count, pad_copy, device_dst,
-                                            hip_stream ? static_cast<hipStream_t>(hip_stream) : dec->gpu->stream);
-        return s.ok() ? ok() : fail(s);
-    });
+    return pack_slot_tensor(dec, RegionPack{spec, resize}, regions, count, pad, device_dst, dst_bytes, hip_stream);
 }
 
 int compeg_batch_pack_tensor_regions(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_resize_spec *resize,
                                      const compeg_region *regions, size_t count, const float *pad, void *device_dst, size_t dst_bytes,
                                      void *hip_stream)
 {
-    return guarded([&] {
-        // (what does not depend on the object first: it is checked where no device is)
-        size_t elem = 0, bytes = 0;
-        int rc = check_region_call(spec, resize, regions, count, pad, &elem);
-        if (rc != COMPEG_OK)
-            return rc;
-        if (!batch)
-            return fail(COMPEG_E_INVALID_ARG, "batch is NULL");
-        if (!batch->count || !batch->output_decoded)
-            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
-        if (!region_tensor_bytes(resize, elem, count, &bytes))
-            return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
-        // (the launch's limits and the destination before the list is copied: nothing is allocated for a count no call takes)
-        if (count > 0xffffffffull || !compeg::region_grid_fits(uint32_t(count), *spec, *resize))
-            return fail(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
-        rc = check_tensor_destination(device_dst, dst_bytes, bytes, elem);
-        if (rc != COMPEG_OK)
-            return rc;
-        std::vector<compeg_region> list(count);
-        for (size_t r = 0; r < count; r++) {
-            const std::string which = "region " + std::to_string(r) + ": ";
-            const uint32_t i = regions[r].image;
-            if (i >= batch->count)
-                return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "image " + std::to_string(i) + " is beyond the batch's " +
-                                                   std::to_string(batch->count) + " images").c_str());
-            rc = check_region(regions + r, spec, resize, batch->descs[i].out_w, batch->descs[i].out_h, which, &list[r]);
-            if (rc != COMPEG_OK)
-                return rc;
-        }
-        const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
-        Status s = batch->pack_tensor_regions(*spec, *resize, list.data(), count, pad_copy, device_dst,
-                                              hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream);
-        return s.ok() ? ok() : fail(s);
-    });
+    return pack_slot_tensor(batch, RegionPack{spec, resize}, regions, count, pad, device_dst, dst_bytes, hip_stream);
 }
 
 /* ---- Filtered tensor output ------------------------------------------------ */
@@ -1522,105 +1608,21 @@ int compeg_batch_pack_tensor_regions(compeg_batch *batch, const compeg_tensor_sp
 int compeg_filtered_tensor_shape(const compeg_tensor_spec *spec, const compeg_filter_spec *filter, uint32_t width, uint32_t height,
                                  const compeg_region *region, uint32_t *pre_width, uint32_t *pre_height, size_t *bytes_per_slot)
 {
-    return guarded([&] {
-        size_t elem = 0;
-        int rc = check_tensor_spec(spec, &elem);
-        if (rc == COMPEG_OK)
-            rc = check_filter_spec(filter);
-        compeg_region r{};
-        if (rc == COMPEG_OK)
-            rc = check_filtered_region(region, spec, filter, width, height, "", &r);
-        if (rc != COMPEG_OK)
-            return rc;
-        if (pre_width)
-            *pre_width = r.src.width / spec->downscale;
-        if (pre_height)
-            *pre_height = r.src.height / spec->downscale;
-        if (bytes_per_slot)
-            *bytes_per_slot = size_t(3) * size_t(filter->out_height) * size_t(filter->out_width) * elem;
-        return ok();
-    });
+    return slot_tensor_shape(FilterPack{spec, filter}, region, width, height, pre_width, pre_height, bytes_per_slot);
 }
 
 int compeg_decoder_pack_tensor_filtered(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
                                         const compeg_region *regions, size_t count, const float *pad, void *device_dst, size_t dst_bytes,
                                         void *hip_stream)
 {
-    return guarded([&] {
-        // (what does not depend on the object first: it is checked where no device is)
-        size_t elem = 0, bytes = 0;
-        int rc = check_filtered_call(spec, filter, regions, count, pad, &elem);
-        if (rc != COMPEG_OK)
-            return rc;
-        if (!dec)
-            return fail(COMPEG_E_INVALID_ARG, "dec is NULL");
-        if (!dec->have_last || !dec->out.ptr)
-            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
-        const compeg_resize_spec extent{filter->out_width, filter->out_height, COMPEG_RESIZE_BILINEAR, 0u};
-        if (!region_tensor_bytes(&extent, elem, count, &bytes))
-            return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
-        // (the launch's limits and the destination before the list is copied: nothing is allocated for a count no call takes)
-        if (count > 0xffffffffull || !compeg::filter_grid_fits(uint32_t(count), *spec, *filter))
-            return fail(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
-        rc = check_tensor_destination(device_dst, dst_bytes, bytes, elem);
-        if (rc != COMPEG_OK)
-            return rc;
-        // (the copy of the caller's list: src and dst as whole rectangles)
-        std::vector<compeg_region> list(count);
-        for (size_t r = 0; r < count; r++) {
-            const std::string which = "region " + std::to_string(r) + ": ";
-            if (regions[r].image != 0u)
-                return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "image " + std::to_string(regions[r].image) + ", a decoder has image 0 only").c_str());
-            rc = check_filtered_region(regions + r, spec, filter, dec->last_w, dec->last_h, which, &list[r]);
-            if (rc != COMPEG_OK)
-                return rc;
-        }
-        const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
-        Status s = dec->pack_tensor_filtered(*spec, *filter, list.data(), count, pad_copy, device_dst,
-                                             hip_stream ? static_cast<hipStream_t>(hip_stream) : dec->gpu->stream);
-        return s.ok() ? ok() : fail(s);
-    });
+    return pack_slot_tensor(dec, FilterPack{spec, filter}, regions, count, pad, device_dst, dst_bytes, hip_stream);
 }
 
 int compeg_batch_pack_tensor_filtered(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
                                       const compeg_region *regions, size_t count, const float *pad, void *device_dst, size_t dst_bytes,
                                       void *hip_stream)
 {
-    return guarded([&] {
-        // (what does not depend on the object first: it is checked where no device is)
-        size_t elem = 0, bytes = 0;
-        int rc = check_filtered_call(spec, filter, regions, count, pad, &elem);
-        if (rc != COMPEG_OK)
-            return rc;
-        if (!batch)
-            return fail(COMPEG_E_INVALID_ARG, "batch is NULL");
-        if (!batch->count || !batch->output_decoded)
-            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
-        const compeg_resize_spec extent{filter->out_width, filter->out_height, COMPEG_RESIZE_BILINEAR, 0u};
-        if (!region_tensor_bytes(&extent, elem, count, &bytes))
-            return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
-        // (the launch's limits and the destination before the list is copied: nothing is allocated for a count no call takes)
-        if (count > 0xffffffffull || !compeg::filter_grid_fits(uint32_t(count), *spec, *filter))
-            return fail(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
-        rc = check_tensor_destination(device_dst, dst_bytes, bytes, elem);
-        if (rc != COMPEG_OK)
-            return rc;
-        std::vector<compeg_region> list(count);
-        for (size_t r = 0; r < count; r++) {
-            const std::string which = "region " + std::to_string(r) + ": ";
-            const uint32_t i = regions[r].image;
-            if (i >= batch->count)
-                return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "image " + std::to_string(i) + " is beyond the batch's " +
-                                                   std::to_string(batch->count) + " images").c_str());
-            rc = check_filtered_region(regions + r, spec, filter, batch->descs[i].out_w, batch->descs[i].out_h, which, &list[r]);
-            if (rc != COMPEG_OK)
-                return rc;
-        }
-        const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
-        Status s = batch->pack_tensor_filtered(*spec, *filter, list.data(), count, pad_copy, device_dst,
-                                               hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream);
-        return s.ok() ? ok() : fail(s);
-    });
+    return pack_slot_tensor(batch, FilterPack{spec, filter}, regions, count, pad, device_dst, dst_bytes, hip_stream);
 }
 
 /* ---- Oriented tensor output ------------------------------------------------ */
@@ -1666,141 +1668,21 @@ int compeg_orient_rect(uint32_t upright_width, uint32_t upright_height, uint32_t
 int compeg_oriented_tensor_shape(const compeg_tensor_spec *spec, const compeg_filter_spec *filter, uint32_t width, uint32_t height,
                                  const compeg_oriented_region *region, uint32_t *pre_width, uint32_t *pre_height, size_t *bytes_per_slot)
 {
-    return guarded([&] {
-        size_t elem = 0;
-        int rc = check_tensor_spec(spec, &elem);
-        if (rc == COMPEG_OK)
-            rc = check_filter_spec(filter);
-        compeg_oriented_region r{};
-        if (rc == COMPEG_OK)
-            rc = check_oriented_region(region, spec, filter, width, height, 1u, "", &r);
-        if (rc != COMPEG_OK)
-            return rc;
-        if (pre_width)
-            *pre_width = r.region.src.width / spec->downscale;
-        if (pre_height)
-            *pre_height = r.region.src.height / spec->downscale;
-        if (bytes_per_slot)
-            *bytes_per_slot = size_t(3) * size_t(filter->out_height) * size_t(filter->out_width) * elem;
-        return ok();
-    });
-}
-
-// compeg_decoder_pack_tensor_oriented (channels_last false: nhwc is not looked at) and compeg_decoder_pack_tensor_nhwc (true: nhwc as
-// the caller gave it, NULL included): one road, so that the two families check the same things in the same order.
-static int decoder_pack_oriented(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_filter_spec *filter, bool channels_last,
-                                 const compeg_nhwc_spec *nhwc, const compeg_oriented_region *regions, size_t count, const float *pad,
-                                 void *device_dst, size_t dst_bytes, void *hip_stream)
-{
-    return guarded([&] {
-        // (what does not depend on the object first: it is checked where no device is)
-        size_t elem = 0, bytes = 0;
-        int rc = check_filtered_call(spec, filter, regions ? &regions->region : nullptr, count, pad, &elem);
-        if (rc == COMPEG_OK && channels_last)
-            rc = check_nhwc_spec(nhwc);
-        if (rc != COMPEG_OK)
-            return rc;
-        if (!dec)
-            return fail(COMPEG_E_INVALID_ARG, "dec is NULL");
-        if (!dec->have_last || !dec->out.ptr)
-            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
-        if (!slot_tensor_bytes(filter, channels_last ? nhwc->channels : 3u, elem, count, &bytes))
-            return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
-        // (the launch's limits and the destination before the list is copied: nothing is allocated for a count no call
-        // takes.  Which slot shapes the list needs takes the orientations alone; one above 8 is the list's check to name)
-        bool upright = false, transposed = false;
-        for (size_t r = 0; r < count; r++) {
-            const uint32_t o = regions[r].orientation == COMPEG_ORIENT_FROM_IMAGE ? dec->last_orientation : regions[r].orientation;
-            (o < 5u ? upright : transposed) = true;
-        }
-        if (count > 0xffffffffull || !compeg::orient_grid_fits(uint32_t(count), *spec, *filter, upright, transposed))
-            return fail(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
-        rc = check_tensor_destination(device_dst, dst_bytes, bytes, elem);
-        if (rc != COMPEG_OK)
-            return rc;
-        // (the copy of the caller's list: src as a whole rectangle, dst as dst', the orientation 1..8)
-        std::vector<compeg_oriented_region> list(count);
-        for (size_t r = 0; r < count; r++) {
-            const std::string which = "region " + std::to_string(r) + ": ";
-            if (regions[r].region.image != 0u)
-                return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "image " + std::to_string(regions[r].region.image) + ", a decoder has image 0 only").c_str());
-            rc = check_oriented_region(regions + r, spec, filter, dec->last_w, dec->last_h, dec->last_orientation, which, &list[r]);
-            if (rc != COMPEG_OK)
-                return rc;
-        }
-        const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
-        const hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : dec->gpu->stream;
-        Status s = channels_last ? dec->pack_tensor_nhwc(*spec, *filter, *nhwc, list.data(), count, pad_copy, device_dst, stream)
-                                 : dec->pack_tensor_oriented(*spec, *filter, list.data(), count, pad_copy, device_dst, stream);
-        return s.ok() ? ok() : fail(s);
-    });
+    return slot_tensor_shape(OrientPack{spec, filter, false, nullptr}, region, width, height, pre_width, pre_height, bytes_per_slot);
 }
 
 int compeg_decoder_pack_tensor_oriented(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
                                         const compeg_oriented_region *regions, size_t count, const float *pad, void *device_dst,
                                         size_t dst_bytes, void *hip_stream)
 {
-    return decoder_pack_oriented(dec, spec, filter, false, nullptr, regions, count, pad, device_dst, dst_bytes, hip_stream);
-}
-
-// compeg_batch_pack_tensor_oriented (channels_last false: nhwc is not looked at) and compeg_batch_pack_tensor_nhwc (true: nhwc as
-// the caller gave it, NULL included): one road, so that the two families check the same things in the same order.
-static int batch_pack_oriented(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_filter_spec *filter, bool channels_last,
-                               const compeg_nhwc_spec *nhwc, const compeg_oriented_region *regions, size_t count, const float *pad,
-                               void *device_dst, size_t dst_bytes, void *hip_stream)
-{
-    return guarded([&] {
-        // (what does not depend on the object first: it is checked where no device is)
-        size_t elem = 0, bytes = 0;
-        int rc = check_filtered_call(spec, filter, regions ? &regions->region : nullptr, count, pad, &elem);
-        if (rc == COMPEG_OK && channels_last)
-            rc = check_nhwc_spec(nhwc);
-        if (rc != COMPEG_OK)
-            return rc;
-        if (!batch)
-            return fail(COMPEG_E_INVALID_ARG, "batch is NULL");
-        if (!batch->count || !batch->output_decoded)
-            return fail(COMPEG_E_INVALID_ARG, "tensor: nothing decoded yet");
-        if (!slot_tensor_bytes(filter, channels_last ? nhwc->channels : 3u, elem, count, &bytes))
-            return fail(COMPEG_E_INVALID_ARG, "tensor: the byte count of this many regions does not fit size_t");
-        // (the launch's limits and the destination before the list is copied, as for a decoder)
-        bool upright = false, transposed = false;
-        for (size_t r = 0; r < count; r++) {
-            const uint32_t i = regions[r].region.image;
-            const uint32_t tag = i < batch->orientations.size() ? batch->orientations[i] : 1u;
-            const uint32_t o = regions[r].orientation == COMPEG_ORIENT_FROM_IMAGE ? tag : regions[r].orientation;
-            (o < 5u ? upright : transposed) = true;
-        }
-        if (count > 0xffffffffull || !compeg::orient_grid_fits(uint32_t(count), *spec, *filter, upright, transposed))
-            return fail(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
-        rc = check_tensor_destination(device_dst, dst_bytes, bytes, elem);
-        if (rc != COMPEG_OK)
-            return rc;
-        std::vector<compeg_oriented_region> list(count);
-        for (size_t r = 0; r < count; r++) {
-            const std::string which = "region " + std::to_string(r) + ": ";
-            const uint32_t i = regions[r].region.image;
-            if (i >= batch->count)
-                return fail(COMPEG_E_INVALID_ARG, ("tensor: " + which + "image " + std::to_string(i) + " is beyond the batch's " +
-                                                   std::to_string(batch->count) + " images").c_str());
-            const uint32_t tag = i < batch->orientations.size() ? batch->orientations[i] : 1u;
-            rc = check_oriented_region(regions + r, spec, filter, batch->descs[i].out_w, batch->descs[i].out_h, tag, which, &list[r]);
-            if (rc != COMPEG_OK)
-                return rc;
-        }
-        const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
-        const hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : batch->gpu->stream;
-        Status s = channels_last ? batch->pack_tensor_nhwc(*spec, *filter, *nhwc, list.data(), count, pad_copy, device_dst, stream)
-                                 : batch->pack_tensor_oriented(*spec, *filter, list.data(), count, pad_copy, device_dst, stream);
-        return s.ok() ? ok() : fail(s);
-    });
+    return pack_slot_tensor(dec, OrientPack{spec, filter, false, nullptr}, regions, count, pad, device_dst, dst_bytes, hip_stream);
 }
 
 int compeg_batch_pack_tensor_oriented(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
                                       const compeg_oriented_region *regions, size_t count, const float *pad, void *device_dst,
                                       size_t dst_bytes, void *hip_stream)
 {
-    return batch_pack_oriented(batch, spec, filter, false, nullptr, regions, count, pad, device_dst, dst_bytes, hip_stream);
+    return pack_slot_tensor(batch, OrientPack{spec, filter, false, nullptr}, regions, count, pad, device_dst, dst_bytes, hip_stream);
 }
 
 /* ---- Channels-last tensor output ------------------------------------------- */
@@ -1809,40 +1691,21 @@ int compeg_nhwc_tensor_shape(const compeg_tensor_spec *spec, const compeg_filter
                              uint32_t height, const compeg_oriented_region *region, uint32_t *pre_width, uint32_t *pre_height,
                              size_t *bytes_per_slot)
 {
-    return guarded([&] {
-        size_t elem = 0;
-        int rc = check_tensor_spec(spec, &elem);
-        if (rc == COMPEG_OK)
-            rc = check_filter_spec(filter);
-        if (rc == COMPEG_OK)
-            rc = check_nhwc_spec(nhwc);
-        compeg_oriented_region r{};
-        if (rc == COMPEG_OK)
-            rc = check_oriented_region(region, spec, filter, width, height, 1u, "", &r);
-        if (rc != COMPEG_OK)
-            return rc;
-        if (pre_width)
-            *pre_width = r.region.src.width / spec->downscale;
-        if (pre_height)
-            *pre_height = r.region.src.height / spec->downscale;
-        if (bytes_per_slot)
-            *bytes_per_slot = size_t(filter->out_height) * size_t(filter->out_width) * size_t(nhwc->channels) * elem;
-        return ok();
-    });
+    return slot_tensor_shape(OrientPack{spec, filter, true, nhwc}, region, width, height, pre_width, pre_height, bytes_per_slot);
 }
 
 int compeg_decoder_pack_tensor_nhwc(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
                                     const compeg_nhwc_spec *nhwc, const compeg_oriented_region *regions, size_t count, const float *pad,
                                     void *device_dst, size_t dst_bytes, void *hip_stream)
 {
-    return decoder_pack_oriented(dec, spec, filter, true, nhwc, regions, count, pad, device_dst, dst_bytes, hip_stream);
+    return pack_slot_tensor(dec, OrientPack{spec, filter, true, nhwc}, regions, count, pad, device_dst, dst_bytes, hip_stream);
 }
 
 int compeg_batch_pack_tensor_nhwc(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
                                   const compeg_nhwc_spec *nhwc, const compeg_oriented_region *regions, size_t count, const float *pad,
                                   void *device_dst, size_t dst_bytes, void *hip_stream)
 {
-    return batch_pack_oriented(batch, spec, filter, true, nhwc, regions, count, pad, device_dst, dst_bytes, hip_stream);
+    return pack_slot_tensor(batch, OrientPack{spec, filter, true, nhwc}, regions, count, pad, device_dst, dst_bytes, hip_stream);
 }
 
 } // extern "C"

@@ -2302,22 +2302,65 @@ Status compeg_batch::decode(hipStream_t stream)
     return Status{};
 }
 
-// Tensor output.  Both packs read `out` on a stream of the caller's choice: behind the last decode (the scheme of
+// Tensor output.  Every pack reads `out` on a stream of the caller's choice: behind the last decode (the scheme of
 // compeg_batch::decode for decodes on different streams), and whatever touches `out` next -- a decode, an upload, a
-// read-back: they all order themselves behind last_stream -- behind the pack.
-Status compeg_decoder::pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream)
+// read-back: they all order themselves behind last_stream -- behind the pack.  Each owner says how, once: the two track
+// their decodes differently.
+Status compeg_decoder::order_pack_behind_decode(hipStream_t stream)
 {
-    CG_HIP(hipSetDevice(gpu->device));
     if (!decode_done)
         CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
     if (decode_pending && stream != last_stream)
         CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
-    CG_HIP(launch_pack_tensor(out.ptr, 0, uint32_t(out_pitch), last_w, last_h, 1, spec, dst, stream));
+    return Status{};
+}
+
+Status compeg_decoder::note_pack(hipStream_t stream)
+{
     // (enqueue on another stream waits for this event: now it stands behind the pack as well)
     CG_HIP(hipEventRecord(decode_done, stream));
     decode_pending = true;
     last_stream = stream;
     return Status{};
+}
+
+Status compeg_batch::order_pack_behind_decode(hipStream_t stream)
+{
+    if (decode_recorded && stream != last_stream) {
+        if (!decode_done)
+            CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
+        CG_HIP(hipEventRecord(decode_done, last_stream));
+        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
+    }
+    return Status{};
+}
+
+Status compeg_batch::note_pack(hipStream_t stream)
+{
+    // (no timing events; the next decode on another stream records decode_done on last_stream, behind this)
+    last_stream = stream;
+    return Status{};
+}
+
+Status compeg_decoder::pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream)
+{
+    CG_HIP(hipSetDevice(gpu->device));
+    CG_TRY(order_pack_behind_decode(stream));
+    CG_HIP(launch_pack_tensor(out.ptr, 0, uint32_t(out_pitch), last_w, last_h, 1, spec, dst, stream));
+    return note_pack(stream);
+}
+
+Status compeg_batch::pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream)
+{
+    CG_HIP(hipSetDevice(gpu->device));
+    CG_TRY(order_pack_behind_decode(stream));
+    // images of one size lie one stride apart (upload: out_offset)
+    const size_t stride = count > 1 ? out_offset[1] - out_offset[0] : 0;
+    for (size_t i = 0; i < count; i++)
+        if (descs[i].out != static_cast<uint8_t *>(out.ptr) + out_offset[0] + i * stride || descs[i].out_pitch != descs[0].out_pitch)
+            return Status::error(COMPEG_E_INVALID_ARG, "tensor: the batch's outputs are not evenly spaced");
+    CG_HIP(launch_pack_tensor(descs[0].out, stride, descs[0].out_pitch, descs[0].out_w, descs[0].out_h, uint32_t(count), spec, dst, stream));
+    return note_pack(stream);
 }
 
 // What a pack says when the antialiased form's records and tables could not be made.  (The C layer has checked the crop
@@ -2326,318 +2369,219 @@ static const char kAntialiasNoBlob[] = "tensor: a crop is smaller than the downs
                                        "antialias tables outgrow 2^32 words";
 
 // Resized tensor output: the ordering of pack_tensor; the per-image records -- and, antialiased, the axis tables behind
-// them in the same block -- travel on the pack's own stream in front of the kernel (RecordStage).
+// them in the same block -- travel on the pack's own stream in front of the kernel (RecordStage).  What both owners do
+// with the `bytes` at `host` once they have made them:
+template <class Owner>
+static Status send_resized(Owner &owner, const void *host, size_t bytes, size_t tables_at, uint32_t images, const compeg_tensor_spec &spec,
+                           const compeg_resize_spec &resize, void *dst, hipStream_t stream)
+{
+    CG_TRY(owner.order_pack_behind_decode(stream));
+    const void *records = nullptr;
+    CG_TRY(owner.resize_records.upload(host, bytes, stream, &records));
+    const bool antialias = (resize.filter & COMPEG_RESIZE_ANTIALIAS) != 0u;
+    CG_HIP(antialias ? launch_resize_tensor_antialias(records, tables_at, images, spec, resize, dst, stream)
+                     : launch_resize_tensor(records, images, spec, resize, dst, stream));
+    return owner.note_pack(stream);
+}
+
 Status compeg_decoder::pack_tensor_resized(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_rect &crop,
                                            void *dst, hipStream_t stream)
 {
     CG_HIP(hipSetDevice(gpu->device));
-    const bool antialias = (resize.filter & COMPEG_RESIZE_ANTIALIAS) != 0u;
-    alignas(8) uint8_t record[kResizeRecordBytes];
-    std::vector<uint32_t> blob; // antialiased: the record and its two axis tables
-    size_t tables_at = 0;
-    const AntialiasSource source{out.ptr, uint32_t(out_pitch), crop};
-    if (antialias && !make_antialias_blob(blob, tables_at, &source, 1, spec.downscale, resize.out_width, resize.out_height))
-        return Status::error(COMPEG_E_INVALID_ARG, kAntialiasNoBlob);
-    if (!antialias && !make_resize_record(record, out.ptr, uint32_t(out_pitch), crop, spec.downscale, resize.out_width, resize.out_height))
-        return Status::error(COMPEG_E_INVALID_ARG, "tensor: the crop is smaller than the downscale factor");
-    if (!decode_done)
-        CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
-    if (decode_pending && stream != last_stream)
-        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
-    const void *records = nullptr;
-    if (antialias) {
-        CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &records));
-        CG_HIP(launch_resize_tensor_antialias(records, tables_at, 1, spec, resize, dst, stream));
-    } else {
-        CG_TRY(resize_records.upload(record, sizeof record, stream, &records));
-        CG_HIP(launch_resize_tensor(records, 1, spec, resize, dst, stream));
+    if ((resize.filter & COMPEG_RESIZE_ANTIALIAS) != 0u) {
+        std::vector<uint32_t> blob; // the record and its two axis tables
+        size_t tables_at = 0;
+        const AntialiasSource source{out.ptr, uint32_t(out_pitch), crop};
+        if (!make_antialias_blob(blob, tables_at, &source, 1, spec.downscale, resize.out_width, resize.out_height))
+            return Status::error(COMPEG_E_INVALID_ARG, kAntialiasNoBlob);
+        return send_resized(*this, blob.data(), blob.size() * 4u, tables_at, 1, spec, resize, dst, stream);
     }
-    CG_HIP(hipEventRecord(decode_done, stream));
-    decode_pending = true;
-    last_stream = stream;
-    return Status{};
+    alignas(8) uint8_t record[kResizeRecordBytes];
+    if (!make_resize_record(record, out.ptr, uint32_t(out_pitch), crop, spec.downscale, resize.out_width, resize.out_height))
+        return Status::error(COMPEG_E_INVALID_ARG, "tensor: the crop is smaller than the downscale factor");
+    return send_resized(*this, record, sizeof record, 0, 1, spec, resize, dst, stream);
 }
 
 Status compeg_batch::pack_tensor_resized(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_rect *crops,
                                          void *dst, hipStream_t stream)
 {
     CG_HIP(hipSetDevice(gpu->device));
-    const bool antialias = (resize.filter & COMPEG_RESIZE_ANTIALIAS) != 0u;
-    // (antialiased: the records, then the axis tables, each distinct (extent, output extent) once)
-    std::vector<uint8_t> records(antialias ? 0 : count * kResizeRecordBytes);
-    std::vector<uint32_t> blob;
-    size_t tables_at = 0;
-    if (antialias) {
+    const auto source = [&](size_t i) {
+        return AntialiasSource{descs[i].out, descs[i].out_pitch, crops ? crops[i] : compeg_rect{0, 0, descs[i].out_w, descs[i].out_h}};
+    };
+    if ((resize.filter & COMPEG_RESIZE_ANTIALIAS) != 0u) {
         std::vector<AntialiasSource> sources(count);
         for (size_t i = 0; i < count; i++)
-            sources[i] = AntialiasSource{descs[i].out, descs[i].out_pitch, crops ? crops[i] : compeg_rect{0, 0, descs[i].out_w, descs[i].out_h}};
+            sources[i] = source(i);
+        std::vector<uint32_t> blob; // the records, then the axis tables, each distinct (extent, output extent) once
+        size_t tables_at = 0;
         if (!make_antialias_blob(blob, tables_at, sources.data(), uint32_t(count), spec.downscale, resize.out_width, resize.out_height))
             return Status::error(COMPEG_E_INVALID_ARG, kAntialiasNoBlob);
+        return send_resized(*this, blob.data(), blob.size() * 4u, tables_at, uint32_t(count), spec, resize, dst, stream);
     }
-    for (size_t i = 0; i < count && !antialias; i++) {
-        const compeg_rect whole{0, 0, descs[i].out_w, descs[i].out_h};
-        if (!make_resize_record(records.data() + i * kResizeRecordBytes, descs[i].out, descs[i].out_pitch, crops ? crops[i] : whole, spec.downscale, resize.out_width,
-                               resize.out_height))
+    std::vector<uint8_t> records(count * kResizeRecordBytes);
+    for (size_t i = 0; i < count; i++) {
+        const AntialiasSource s = source(i);
+        if (!make_resize_record(records.data() + i * kResizeRecordBytes, s.src, s.pitch, s.crop, spec.downscale, resize.out_width, resize.out_height))
             return Status::error(COMPEG_E_INVALID_ARG, "tensor: a crop is smaller than the downscale factor");
     }
-    if (decode_recorded && stream != last_stream) {
-        if (!decode_done)
-            CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
-        CG_HIP(hipEventRecord(decode_done, last_stream));
-        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
-    }
-    const void *device_records = nullptr;
-    if (antialias)
-        CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &device_records));
-    else
-        CG_TRY(resize_records.upload(records.data(), records.size(), stream, &device_records));
-    if (antialias)
-        CG_HIP(launch_resize_tensor_antialias(device_records, tables_at, uint32_t(count), spec, resize, dst, stream));
-    else
-        CG_HIP(launch_resize_tensor(device_records, uint32_t(count), spec, resize, dst, stream));
-    // (no timing events; the next decode on another stream records decode_done on last_stream, behind this)
-    last_stream = stream;
-    return Status{};
+    return send_resized(*this, records.data(), records.size(), 0, uint32_t(count), spec, resize, dst, stream);
 }
 
-// What a region pack says when its records and tables could not be made (the C layer has checked crops and ratios).
-static const char kRegionNoBlob[] = "tensor: a region's crop is smaller than the downscale factor or beyond the antialias ratio limit, or this "
-                                    "call's antialias tables outgrow 2^32 words";
+// The slot families -- region, filtered, oriented and channels-last tensor output -- go down one road, pack_slots.  An
+// owner supplies where a region's image lies (and, above, its ordering); a family its grid test, its placement of a
+// slot, its blob, its launch and what it says when the blob could not be made.
+RegionSource compeg_decoder::region_source(const compeg_region &region) const
+{
+    return RegionSource{out.ptr, uint32_t(out_pitch), region.src, region.dst}; // (image 0, the only one)
+}
 
-// Region tensor output: pack_tensor_resized's ordering and staging; one kernel family for the three filters, the
-// records -- and, antialiased, the axis tables behind them -- in one block.
+RegionSource compeg_batch::region_source(const compeg_region &region) const
+{
+    const ImageDesc &d = descs[region.image];
+    return RegionSource{d.out, d.out_pitch, region.src, region.dst};
+}
+
+template <class Owner, class Family>
+static Status pack_slots(Owner &owner, const Family &family, size_t count, hipStream_t stream)
+{
+    CG_HIP(hipSetDevice(owner.gpu->device));
+    // (the limits first: nothing is allocated for a count that no launch takes)
+    if (count > 0xffffffffull || !family.grid_fits(uint32_t(count)))
+        return Status::error(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
+    std::vector<typename Family::Source> placements(count);
+    for (size_t r = 0; r < count; r++)
+        placements[r] = family.source(owner, r);
+    // (the records and, behind them, the axis tables in one block)
+    std::vector<uint32_t> blob;
+    size_t tables_at = 0;
+    if (!family.make_blob(blob, tables_at, placements.data(), uint32_t(count)))
+        return Status::error(COMPEG_E_INVALID_ARG, Family::kNoBlob);
+    CG_TRY(owner.order_pack_behind_decode(stream));
+    const void *records = nullptr;
+    CG_TRY(owner.resize_records.upload(blob.data(), blob.size() * 4u, stream, &records));
+    CG_HIP(family.launch(records, tables_at, uint32_t(count), stream));
+    return owner.note_pack(stream);
+}
+
+namespace {
+
+// Region tensor output: one kernel family for the three filters.
+struct RegionFamily {
+    using Source = RegionSource;
+    // (the C layer has checked crops and ratios)
+    static constexpr const char *kNoBlob = "tensor: a region's crop is smaller than the downscale factor or beyond the antialias ratio limit, or "
+                                           "this call's antialias tables outgrow 2^32 words";
+    const compeg_tensor_spec &spec;
+    const compeg_resize_spec &resize;
+    const compeg_region *regions;
+    const float *pad;
+    void *dst;
+    bool grid_fits(uint32_t slots) const { return region_grid_fits(slots, spec, resize); }
+    template <class Owner>
+    Source source(const Owner &owner, size_t r) const { return owner.region_source(regions[r]); }
+    bool make_blob(std::vector<uint32_t> &blob, size_t &tables_at, const Source *sources, uint32_t slots) const
+    {
+        return make_region_blob(blob, tables_at, sources, slots, spec.downscale, resize.filter);
+    }
+    hipError_t launch(const void *records, size_t tables_at, uint32_t slots, hipStream_t stream) const
+    {
+        return launch_region_tensor(records, tables_at, slots, spec, resize, pad, dst, stream);
+    }
+};
+
+// Filtered tensor output: the filter kernels' tables and launch.
+struct FilterFamily {
+    using Source = RegionSource;
+    // (the C layer has checked crops and taps)
+    static constexpr const char *kNoBlob = "tensor: a region's crop is smaller than the downscale factor or beyond the kernel's tap limit, or "
+                                           "this call's filter tables outgrow 2^32 words";
+    const compeg_tensor_spec &spec;
+    const compeg_filter_spec &filter;
+    const compeg_region *regions;
+    const float *pad;
+    void *dst;
+    bool grid_fits(uint32_t slots) const { return filter_grid_fits(slots, spec, filter); }
+    template <class Owner>
+    Source source(const Owner &owner, size_t r) const { return owner.region_source(regions[r]); }
+    bool make_blob(std::vector<uint32_t> &blob, size_t &tables_at, const Source *sources, uint32_t slots) const
+    {
+        return make_filter_blob(blob, tables_at, sources, slots, spec.downscale, filter.kernel);
+    }
+    hipError_t launch(const void *records, size_t tables_at, uint32_t slots, hipStream_t stream) const
+    {
+        return launch_filter_tensor(records, tables_at, slots, spec, filter, pad, dst, stream);
+    }
+};
+
+// Oriented tensor output: the orient kernels' records and launch -- and channels-last tensor output, the same blob and
+// grid to the nhwc kernels' launch.
+struct OrientFamily {
+    using Source = OrientSource;
+    static constexpr const char *kNoBlob = FilterFamily::kNoBlob;
+    const compeg_tensor_spec &spec;
+    const compeg_filter_spec &filter;
+    const compeg_nhwc_spec *nhwc; // null: the planes
+    const compeg_oriented_region *regions;
+    const float *pad;
+    void *dst;
+    // which of the two slot shapes the list needs: T is the upright extent (1..4) or the transposed one (5..8)
+    bool upright = false, transposed = false;
+    OrientFamily(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
+                 const compeg_oriented_region *regions, size_t count, const float *pad, void *dst)
+        : spec(spec), filter(filter), nhwc(nhwc), regions(regions), pad(pad), dst(dst)
+    {
+        for (size_t r = 0; r < count; r++)
+            (regions[r].orientation < 5u ? upright : transposed) = true;
+    }
+    bool grid_fits(uint32_t slots) const { return orient_grid_fits(slots, spec, filter, upright, transposed); }
+    template <class Owner>
+    Source source(const Owner &owner, size_t r) const { return Source{owner.region_source(regions[r].region), regions[r].orientation}; }
+    bool make_blob(std::vector<uint32_t> &blob, size_t &tables_at, const Source *sources, uint32_t slots) const
+    {
+        return make_orient_blob(blob, tables_at, sources, slots, spec.downscale, filter.kernel, filter.out_width, filter.out_height);
+    }
+    hipError_t launch(const void *records, size_t tables_at, uint32_t slots, hipStream_t stream) const
+    {
+        return nhwc ? launch_nhwc_tensor(records, tables_at, slots, spec, filter, *nhwc, upright, transposed, pad, dst, stream)
+                    : launch_orient_tensor(records, tables_at, slots, spec, filter, upright, transposed, pad, dst, stream);
+    }
+};
+
+} // namespace
+
 Status compeg_decoder::pack_tensor_regions(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_region *regions,
                                            size_t count, const float *pad, void *dst, hipStream_t stream)
 {
-    CG_HIP(hipSetDevice(gpu->device));
-    // (the limits first: nothing is allocated for a count that no launch takes)
-    if (count > 0xffffffffull || !region_grid_fits(uint32_t(count), spec, resize))
-        return Status::error(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
-    std::vector<RegionSource> placements(count);
-    for (size_t r = 0; r < count; r++)
-        placements[r] = RegionSource{out.ptr, uint32_t(out_pitch), regions[r].src, regions[r].dst};
-    std::vector<uint32_t> blob;
-    size_t tables_at = 0;
-    if (!make_region_blob(blob, tables_at, placements.data(), uint32_t(count), spec.downscale, resize.filter))
-        return Status::error(COMPEG_E_INVALID_ARG, kRegionNoBlob);
-    if (!decode_done)
-        CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
-    if (decode_pending && stream != last_stream)
-        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
-    const void *records = nullptr;
-    CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &records));
-    CG_HIP(launch_region_tensor(records, tables_at, uint32_t(count), spec, resize, pad, dst, stream));
-    CG_HIP(hipEventRecord(decode_done, stream));
-    decode_pending = true;
-    last_stream = stream;
-    return Status{};
+    return pack_slots(*this, RegionFamily{spec, resize, regions, pad, dst}, count, stream);
 }
 
 Status compeg_batch::pack_tensor_regions(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_region *regions,
                                          size_t count, const float *pad, void *dst, hipStream_t stream)
 {
-    CG_HIP(hipSetDevice(gpu->device));
-    // (the limits first: nothing is allocated for a count that no launch takes)
-    if (count > 0xffffffffull || !region_grid_fits(uint32_t(count), spec, resize))
-        return Status::error(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
-    std::vector<RegionSource> placements(count);
-    for (size_t r = 0; r < count; r++) {
-        const ImageDesc &d = descs[regions[r].image];
-        placements[r] = RegionSource{d.out, d.out_pitch, regions[r].src, regions[r].dst};
-    }
-    std::vector<uint32_t> blob;
-    size_t tables_at = 0;
-    if (!make_region_blob(blob, tables_at, placements.data(), uint32_t(count), spec.downscale, resize.filter))
-        return Status::error(COMPEG_E_INVALID_ARG, kRegionNoBlob);
-    if (decode_recorded && stream != last_stream) {
-        if (!decode_done)
-            CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
-        CG_HIP(hipEventRecord(decode_done, last_stream));
-        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
-    }
-    const void *device_records = nullptr;
-    CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &device_records));
-    CG_HIP(launch_region_tensor(device_records, tables_at, uint32_t(count), spec, resize, pad, dst, stream));
-    // (no timing events; the next decode on another stream records decode_done on last_stream, behind this)
-    last_stream = stream;
-    return Status{};
+    return pack_slots(*this, RegionFamily{spec, resize, regions, pad, dst}, count, stream);
 }
 
-// What a filtered pack says when its records and tables could not be made (the C layer has checked crops and taps).
-static const char kFilterNoBlob[] = "tensor: a region's crop is smaller than the downscale factor or beyond the kernel's tap limit, or this "
-                                    "call's filter tables outgrow 2^32 words";
-
-// Filtered tensor output: pack_tensor_regions' ordering and staging with the filter kernels' tables and launch.
 Status compeg_decoder::pack_tensor_filtered(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_region *regions,
                                             size_t count, const float *pad, void *dst, hipStream_t stream)
 {
-    CG_HIP(hipSetDevice(gpu->device));
-    // (the limits first: nothing is allocated for a count that no launch takes)
-    if (count > 0xffffffffull || !filter_grid_fits(uint32_t(count), spec, filter))
-        return Status::error(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
-    std::vector<RegionSource> placements(count);
-    for (size_t r = 0; r < count; r++)
-        placements[r] = RegionSource{out.ptr, uint32_t(out_pitch), regions[r].src, regions[r].dst};
-    std::vector<uint32_t> blob;
-    size_t tables_at = 0;
-    if (!make_filter_blob(blob, tables_at, placements.data(), uint32_t(count), spec.downscale, filter.kernel))
-        return Status::error(COMPEG_E_INVALID_ARG, kFilterNoBlob);
-    if (!decode_done)
-        CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
-    if (decode_pending && stream != last_stream)
-        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
-    const void *records = nullptr;
-    CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &records));
-    CG_HIP(launch_filter_tensor(records, tables_at, uint32_t(count), spec, filter, pad, dst, stream));
-    CG_HIP(hipEventRecord(decode_done, stream));
-    decode_pending = true;
-    last_stream = stream;
-    return Status{};
+    return pack_slots(*this, FilterFamily{spec, filter, regions, pad, dst}, count, stream);
 }
 
 Status compeg_batch::pack_tensor_filtered(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_region *regions,
                                           size_t count, const float *pad, void *dst, hipStream_t stream)
 {
-    CG_HIP(hipSetDevice(gpu->device));
-    // (the limits first: nothing is allocated for a count that no launch takes)
-    if (count > 0xffffffffull || !filter_grid_fits(uint32_t(count), spec, filter))
-        return Status::error(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
-    std::vector<RegionSource> placements(count);
-    for (size_t r = 0; r < count; r++) {
-        const ImageDesc &d = descs[regions[r].image];
-        placements[r] = RegionSource{d.out, d.out_pitch, regions[r].src, regions[r].dst};
-    }
-    std::vector<uint32_t> blob;
-    size_t tables_at = 0;
-    if (!make_filter_blob(blob, tables_at, placements.data(), uint32_t(count), spec.downscale, filter.kernel))
-        return Status::error(COMPEG_E_INVALID_ARG, kFilterNoBlob);
-    if (decode_recorded && stream != last_stream) {
-        if (!decode_done)
-            CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
-        CG_HIP(hipEventRecord(decode_done, last_stream));
-        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
-    }
-    const void *device_records = nullptr;
-    CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &device_records));
-    CG_HIP(launch_filter_tensor(device_records, tables_at, uint32_t(count), spec, filter, pad, dst, stream));
-    // (no timing events; the next decode on another stream records decode_done on last_stream, behind this)
-    last_stream = stream;
-    return Status{};
+    return pack_slots(*this, FilterFamily{spec, filter, regions, pad, dst}, count, stream);
 }
 
-// Oriented tensor output: pack_tensor_filtered's ordering and staging with the orient kernels' records and launch -- and
-// channels-last tensor output, the same road to the nhwc kernels' launch: pack_oriented with nhwc, null for the planes.
-// Which of the two slot shapes a list needs: T is the upright extent (1..4) or the transposed one (5..8).
-static void orient_shapes(const compeg_oriented_region *regions, size_t count, bool &upright, bool &transposed)
+Status compeg_decoder::pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
+                                            const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream)
 {
-    upright = transposed = false;
-    for (size_t r = 0; r < count; r++)
-        (regions[r].orientation < 5u ? upright : transposed) = true;
+    return pack_slots(*this, OrientFamily(spec, filter, nhwc, regions, count, pad, dst), count, stream);
 }
 
-Status compeg_decoder::pack_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
-                                     const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream)
+Status compeg_batch::pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
+                                          const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream)
 {
-    CG_HIP(hipSetDevice(gpu->device));
-    bool upright = false, transposed = false;
-    orient_shapes(regions, count, upright, transposed);
-    // (the limits first: nothing is allocated for a count that no launch takes)
-    if (count > 0xffffffffull || !orient_grid_fits(uint32_t(count), spec, filter, upright, transposed))
-        return Status::error(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
-    std::vector<OrientSource> placements(count);
-    for (size_t r = 0; r < count; r++)
-        placements[r] = OrientSource{RegionSource{out.ptr, uint32_t(out_pitch), regions[r].region.src, regions[r].region.dst}, regions[r].orientation};
-    std::vector<uint32_t> blob;
-    size_t tables_at = 0;
-    if (!make_orient_blob(blob, tables_at, placements.data(), uint32_t(count), spec.downscale, filter.kernel, filter.out_width, filter.out_height))
-        return Status::error(COMPEG_E_INVALID_ARG, kFilterNoBlob);
-    if (!decode_done)
-        CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
-    if (decode_pending && stream != last_stream)
-        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
-    const void *records = nullptr;
-    CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &records));
-    CG_HIP(nhwc ? launch_nhwc_tensor(records, tables_at, uint32_t(count), spec, filter, *nhwc, upright, transposed, pad, dst, stream)
-                : launch_orient_tensor(records, tables_at, uint32_t(count), spec, filter, upright, transposed, pad, dst, stream));
-    CG_HIP(hipEventRecord(decode_done, stream));
-    decode_pending = true;
-    last_stream = stream;
-    return Status{};
-}
-
-Status compeg_batch::pack_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
-                                   const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream)
-{
-    CG_HIP(hipSetDevice(gpu->device));
-    bool upright = false, transposed = false;
-    orient_shapes(regions, count, upright, transposed);
-    // (the limits first: nothing is allocated for a count that no launch takes)
-    if (count > 0xffffffffull || !orient_grid_fits(uint32_t(count), spec, filter, upright, transposed))
-        return Status::error(COMPEG_E_INVALID_ARG, "tensor: the grid of this many regions of this output extent does not fit one launch");
-    std::vector<OrientSource> placements(count);
-    for (size_t r = 0; r < count; r++) {
-        const ImageDesc &d = descs[regions[r].region.image];
-        placements[r] = OrientSource{RegionSource{d.out, d.out_pitch, regions[r].region.src, regions[r].region.dst}, regions[r].orientation};
-    }
-    std::vector<uint32_t> blob;
-    size_t tables_at = 0;
-    if (!make_orient_blob(blob, tables_at, placements.data(), uint32_t(count), spec.downscale, filter.kernel, filter.out_width, filter.out_height))
-        return Status::error(COMPEG_E_INVALID_ARG, kFilterNoBlob);
-    if (decode_recorded && stream != last_stream) {
-        if (!decode_done)
-            CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
-        CG_HIP(hipEventRecord(decode_done, last_stream));
-        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
-    }
-    const void *device_records = nullptr;
-    CG_TRY(resize_records.upload(blob.data(), blob.size() * 4u, stream, &device_records));
-    CG_HIP(nhwc ? launch_nhwc_tensor(device_records, tables_at, uint32_t(count), spec, filter, *nhwc, upright, transposed, pad, dst, stream)
-                : launch_orient_tensor(device_records, tables_at, uint32_t(count), spec, filter, upright, transposed, pad, dst, stream));
-    // (no timing events; the next decode on another stream records decode_done on last_stream, behind this)
-    last_stream = stream;
-    return Status{};
-}
-
-Status compeg_decoder::pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_oriented_region *regions,
-                                            size_t count, const float *pad, void *dst, hipStream_t stream)
-{
-    return pack_oriented(spec, filter, nullptr, regions, count, pad, dst, stream);
-}
-
-Status compeg_decoder::pack_tensor_nhwc(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec &nhwc,
-                                        const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream)
-{
-    return pack_oriented(spec, filter, &nhwc, regions, count, pad, dst, stream);
-}
-
-Status compeg_batch::pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_oriented_region *regions,
-                                          size_t count, const float *pad, void *dst, hipStream_t stream)
-{
-    return pack_oriented(spec, filter, nullptr, regions, count, pad, dst, stream);
-}
-
-Status compeg_batch::pack_tensor_nhwc(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec &nhwc,
-                                      const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream)
-{
-    return pack_oriented(spec, filter, &nhwc, regions, count, pad, dst, stream);
-}
-
-Status compeg_batch::pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream)
-{
-    CG_HIP(hipSetDevice(gpu->device));
-    if (decode_recorded && stream != last_stream) {
-        if (!decode_done)
-            CG_HIP(hipEventCreateWithFlags(&decode_done, hipEventDisableTiming));
-        CG_HIP(hipEventRecord(decode_done, last_stream));
-        CG_HIP(hipStreamWaitEvent(stream, decode_done, 0));
-    }
-    // images of one size lie one stride apart (upload: out_offset)
-    const size_t stride = count > 1 ? out_offset[1] - out_offset[0] : 0;
-    for (size_t i = 0; i < count; i++)
-        if (descs[i].out != static_cast<uint8_t *>(out.ptr) + out_offset[0] + i * stride || descs[i].out_pitch != descs[0].out_pitch)
-            return Status::error(COMPEG_E_INVALID_ARG, "tensor: the batch's outputs are not evenly spaced");
-    CG_HIP(launch_pack_tensor(descs[0].out, stride, descs[0].out_pitch, descs[0].out_w, descs[0].out_h, uint32_t(count), spec, dst, stream));
-    // (no timing events; the next decode on another stream records decode_done on last_stream, behind this)
-    last_stream = stream;
-    return Status{};
+    return pack_slots(*this, OrientFamily(spec, filter, nhwc, regions, count, pad, dst), count, stream);
 }

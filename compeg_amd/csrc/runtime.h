@@ -152,27 +152,29 @@ struct compeg_decoder {
     // Tensor output (compeg_hip.h): the last image's corner of `out`, packed on `stream` behind the last decode; the next
     // decode waits for it.  spec and dst: checked by the caller.
     compeg::Status pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream);
+    // ... which is every pack's ordering: the first orders what `stream` does next behind the last decode, the second
+    // notes, behind the pack's last call, that a pack was recorded on `stream`
+    compeg::Status order_pack_behind_decode(hipStream_t stream);
+    compeg::Status note_pack(hipStream_t stream);
     // Resized tensor output: the same ordering; crop lies inside the last image (checked by the caller, like the specs)
     compeg::RecordStage resize_records;
     compeg::Status pack_tensor_resized(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_rect &crop,
                                        void *dst, hipStream_t stream);
+    // The slot families, all down one road (runtime.cpp: pack_slots), which asks the owner for a region's placement:
+    // where its image lies (image 0, the last image, whatever the region says) with the region's rectangles
+    compeg::RegionSource region_source(const compeg_region &region) const;
     // Region tensor output: `count` slots, each a crop of the last image into a rectangle of its slot; src and dst are
     // whole rectangles by now, and inside the image and the output (checked by the caller, like specs, pad and dst)
     compeg::Status pack_tensor_regions(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_region *regions,
                                        size_t count, const float *pad, void *dst, hipStream_t stream);
-    // Filtered tensor output: pack_tensor_regions with one of the four resampling kernels (the tap limit checked by the caller too)
+    // Filtered tensor output: one of the four resampling kernels (the tap limit checked by the caller too)
     compeg::Status pack_tensor_filtered(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_region *regions,
                                         size_t count, const float *pad, void *dst, hipStream_t stream);
-    // Oriented tensor output: pack_tensor_filtered through an orientation per slot; every region's dst is dst' (inside T) and
-    // its orientation 1..8 by now (checked by the caller, like everything else)
-    compeg::Status pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_oriented_region *regions,
-                                        size_t count, const float *pad, void *dst, hipStream_t stream);
-    // Channels-last tensor output: pack_tensor_oriented into [count][oh][ow][C]; nhwc checked by the caller.  Both go through
-    // pack_oriented (nhwc null: the planes)
-    compeg::Status pack_tensor_nhwc(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec &nhwc,
-                                    const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
-    compeg::Status pack_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
-                                 const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
+    // Oriented tensor output: an orientation per slot; every region's dst is dst' (inside T) and its orientation 1..8 by
+    // now (checked by the caller, like everything else).  nhwc null: the planes; else channels-last tensor output, into
+    // [count][oh][ow][C], nhwc checked by the caller
+    compeg::Status pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
+                                        const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
     compeg::Status check_scan_result(bool &fell_back);
     compeg::Status preprocess_on_device(const compeg::ImageData &img, hipStream_t stream, uint32_t &nwords,
                                         uint32_t &nstarts, uint32_t &span, bool &fell_back, size_t blob_bytes,
@@ -269,26 +271,28 @@ struct compeg_batch {
     bool output_decoded = false; // `out` holds a decode of the images uploaded last
     // Tensor output (compeg_hip.h): every image's output (all of one size: checked by the caller, like spec and dst)
     compeg::Status pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream);
+    // ... and every pack's ordering, in the batch's own scheme (it records decode_done only when a stream changes): `stream`
+    // behind the last decode on another stream, and afterwards the note that a pack was recorded on `stream`
+    compeg::Status order_pack_behind_decode(hipStream_t stream);
+    compeg::Status note_pack(hipStream_t stream);
     // Resized tensor output: images of any sizes; crops: one per image, each inside its image (checked by the caller)
     compeg::RecordStage resize_records;
     compeg::Status pack_tensor_resized(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_rect *crops,
                                        void *dst, hipStream_t stream);
+    // The slot families, all down one road (runtime.cpp: pack_slots), which asks the owner for a region's placement:
+    // where image region.image lies (below count: checked by the caller) with the region's rectangles
+    compeg::RegionSource region_source(const compeg_region &region) const;
     // Region tensor output: `count` slots, each a crop of image regions[r].image; src and dst are whole rectangles by
     // now, and inside their image and the output (checked by the caller, like specs, pad and dst)
     compeg::Status pack_tensor_regions(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_region *regions,
                                        size_t count, const float *pad, void *dst, hipStream_t stream);
-    // Filtered tensor output: pack_tensor_regions with one of the four resampling kernels (the tap limit checked by the caller too)
+    // Filtered tensor output: one of the four resampling kernels (the tap limit checked by the caller too)
     compeg::Status pack_tensor_filtered(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_region *regions,
                                         size_t count, const float *pad, void *dst, hipStream_t stream);
-    // Oriented tensor output: pack_tensor_filtered through an orientation per slot; every region's dst is dst' (inside T) and
-    // its orientation 1..8 by now (checked by the caller, like everything else)
-    compeg::Status pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_oriented_region *regions,
-                                        size_t count, const float *pad, void *dst, hipStream_t stream);
-    // Channels-last tensor output: pack_tensor_oriented into [count][oh][ow][C]; nhwc checked by the caller.  Both go through
-    // pack_oriented (nhwc null: the planes)
-    compeg::Status pack_tensor_nhwc(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec &nhwc,
-                                    const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
-    compeg::Status pack_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
-                                 const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
+    // Oriented tensor output: an orientation per slot; every region's dst is dst' (inside T) and its orientation 1..8 by
+    // now (checked by the caller, like everything else).  nhwc null: the planes; else channels-last tensor output, into
+    // [count][oh][ow][C], nhwc checked by the caller
+    compeg::Status pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
+                                        const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
     std::vector<uint32_t> orientations; // the EXIF orientation tag of every image of the last upload (note_batch_properties)
 };

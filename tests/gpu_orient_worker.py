@@ -304,8 +304,57 @@ def back_to_back():
         _check(dst[2][r], fr.expected(frames[image][1], size, 1, "f16", scale, bias, "rgb", "triangle", src, rect, GREY), "f16", f"filtered pack behind them, region {r}")
 
 
+# two slots of (13, 5) out of a 17x9 frame, FIVE's smallest with a picture in it (synth's 16x8 is black, as fresh memory may be)
+ACROSS = ((0, None, None, 6), (0, (1, 0, 15, 8), (2, 1, 9, 3), 3))
+
+
+def _check_across(dst, rgba, what):
+    for r, (_, src, rect, o) in enumerate(ACROSS):
+        _check(dst[r], orf.expected(rgba, (13, 5), 1, "f32", (1, 1, 1), (0, 0, 0), "rgb", "bicubic", src, rect, COLOURS, o), "f32", f"{what}, region {r}")
+
+
+def decoder_ordering_without_host_waits():
+    """enqueue(img1, A), pack(dst1, B), enqueue(img2, A), pack(dst2, B) on a new decoder, two 17x9 frames: every pack behind
+    its decode, the second decode behind the first pack, with nothing but the streams' own order and the library's events."""
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    (j1, r1), (j2, r2) = fr.frame(17, 9, seed=21), fr.frame(17, 9, seed=31)
+    img1, img2 = ca.ImageData(j1), ca.ImageData(j2)
+    dst1, dst2 = _fresh(2, (13, 5), "f32"), _fresh(2, (13, 5), "f32")
+    torch.cuda.synchronize()
+    dec = ca.Decoder(gpu)
+    dec.enqueue(img1, a.cuda_stream)
+    dec.pack_tensor_oriented(dst1, (13, 5), ACROSS, pad=COLOURS, dtype="f32", hip_stream=b.cuda_stream)
+    dec.enqueue(img2, a.cuda_stream)
+    dec.pack_tensor_oriented(dst2, (13, 5), ACROSS, pad=COLOURS, dtype="f32", hip_stream=b.cuda_stream)
+    a.synchronize()
+    b.synchronize()
+    _check_across(dst1, r1, "first frame")
+    _check_across(dst2, r2, "second frame")
+
+
+def batch_ordering_without_host_waits():
+    """The same on a new batch of one 17x9 frame: decode(A), pack(dst1, B), decode(A), pack(dst2, B) and one wait().  The
+    first pack stands behind the first decode -- the batch's output holds nothing before it --, the second decode behind
+    the first pack, the second pack behind the second decode."""
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    jpeg, rgba = fr.frame(17, 9, seed=21)
+    dst1, dst2 = _fresh(2, (13, 5), "f32"), _fresh(2, (13, 5), "f32")
+    torch.cuda.synchronize()
+    batch = ca.Batch(gpu)
+    batch.upload([ca.ImageData(jpeg)])
+    batch.decode(hip_stream=a.cuda_stream)
+    batch.pack_tensor_oriented(dst1, (13, 5), ACROSS, pad=COLOURS, dtype="f32", hip_stream=b.cuda_stream)
+    batch.decode(hip_stream=a.cuda_stream)
+    batch.pack_tensor_oriented(dst2, (13, 5), ACROSS, pad=COLOURS, dtype="f32", hip_stream=b.cuda_stream)
+    batch.wait()
+    a.synchronize()
+    _check_across(dst1, rgba, "first pack")
+    _check_across(dst2, rgba, "second pack")
+
+
 CASES = {fn.__name__: (fn, ()) for fn in (every_orientation, orientation_1_is_the_filtered_pack, eight_on_a_batch_of_five, run_edges, portrait_letterbox,
-                                          more_than_one_workgroup_per_band, the_tag, rejections, back_to_back)}
+                                          more_than_one_workgroup_per_band, the_tag, rejections, back_to_back,
+                                          decoder_ordering_without_host_waits, batch_ordering_without_host_waits)}
 
 
 def main(out_path):
