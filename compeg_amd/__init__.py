@@ -421,14 +421,15 @@ class Gpu:
 class ImageData:
     """A parsed JPEG (ref: `ImageData`, src/lib.rs:576-851)."""
 
-    def __init__(self, jpeg, copy=True, allow_sampling=False, standard_entropy=False):
+    def __init__(self, jpeg, copy=True, allow_sampling=False, standard_entropy=False, allow_grayscale=False):
         """Extensions beyond the reference (compeg_image_parse_ext): allow_sampling -- 4:4:4, 4:4:0 and
         4:2:0 are accepted as well as 4:2:2; standard_entropy -- the bit reader is topped up in front of
-        DC codes and ZRL skips 16 positions, as ITU-T T.81 has it (the reference deviates in both)."""
+        DC codes and ZRL skips 16 positions, as ITU-T T.81 has it (the reference deviates in both);
+        allow_grayscale -- frames with one component are accepted and decode to R = G = B = luma."""
         self._h = None
         self._keep = _host_view(jpeg)
         h = C.c_void_p()
-        flags = (1 if allow_sampling else 0) | (2 if standard_entropy else 0)
+        flags = (1 if allow_sampling else 0) | (2 if standard_entropy else 0) | (4 if allow_grayscale else 0)
         if flags:
             check(lib.compeg_image_parse_ext(self._keep.ctypes.data, self._keep.nbytes, 1 if copy else 0, flags,
                                              C.byref(h)))
@@ -448,6 +449,10 @@ class ImageData:
 
     def parallelism(self):
         return lib.compeg_image_parallelism(self._h)
+
+    def components(self):
+        """Extension (compeg_image_components): 3, or 1 for a grayscale image (allow_grayscale)."""
+        return lib.compeg_image_components(self._h)
 
     @property
     def orientation(self):
@@ -723,18 +728,18 @@ class Batch:
         arr = (C.c_void_p * len(self._images))(*[im._h for im in self._images])
         check(lib.compeg_batch_upload(self._h, arr, len(self._images), host_threads))
 
-    def upload_jpegs(self, jpegs, host_threads=0, allow_sampling=False, standard_entropy=False):
+    def upload_jpegs(self, jpegs, host_threads=0, allow_sampling=False, standard_entropy=False, allow_grayscale=False):
         """Host-fed use: parse (on the worker threads), preprocess, upload.  jpegs: bytes-like objects, or a
         JpegList made from them once (saves this wrapper's per-call pointer gathering, nothing else)."""
         jl = jpegs if isinstance(jpegs, JpegList) else JpegList(jpegs)
-        flags = (1 if allow_sampling else 0) | (2 if standard_entropy else 0)
+        flags = (1 if allow_sampling else 0) | (2 if standard_entropy else 0) | (4 if allow_grayscale else 0)
         self._images = []
         check(lib.compeg_batch_upload_jpegs(self._h, jl.ptrs, jl.lens, jl.count, host_threads, flags))
 
-    def upload_jpegs_begin(self, jpegs, host_threads=0, allow_sampling=False, standard_entropy=False):
+    def upload_jpegs_begin(self, jpegs, host_threads=0, allow_sampling=False, standard_entropy=False, allow_grayscale=False):
         """compeg_batch_upload_jpegs_begin: returns when the transfers are queued; upload_end() (or decode()) finishes."""
         jl = jpegs if isinstance(jpegs, JpegList) else JpegList(jpegs)
-        flags = (1 if allow_sampling else 0) | (2 if standard_entropy else 0)
+        flags = (1 if allow_sampling else 0) | (2 if standard_entropy else 0) | (4 if allow_grayscale else 0)
         self._images = []
         self._feeding = jl   # (the bytes stay alive until the upload has ended)
         check(lib.compeg_batch_upload_jpegs_begin(self._h, jl.ptrs, jl.lens, jl.count, host_threads, flags))

@@ -84,6 +84,7 @@ def _load():
         "compeg_image_width": (u32, [vp]),
         "compeg_image_height": (u32, [vp]),
         "compeg_image_parallelism": (u32, [vp]),
+        "compeg_image_components": (u32, [vp]),
         "compeg_image_metadata": (vp, [vp]),
         "compeg_image_huffman_l1": (vp, [vp]),
         "compeg_image_huffman_l2": (vp, [vp, psz]),

@@ -638,7 +638,7 @@ int compeg_image_parse_ext(const uint8_t *jpeg, size_t len, int copy, unsigned f
         if (!out)
             return fail(COMPEG_E_INVALID_ARG, "out is NULL");
         *out = nullptr;
-        if (flags & ~(COMPEG_PARSE_ANY_LUMA_SAMPLING | COMPEG_PARSE_STANDARD_ENTROPY))
+        if (flags & ~(COMPEG_PARSE_ANY_LUMA_SAMPLING | COMPEG_PARSE_STANDARD_ENTROPY | COMPEG_PARSE_GRAYSCALE))
             return fail(COMPEG_E_INVALID_ARG, "unknown parse flags");
         ImageData *d = nullptr;
         Status s = ImageData::parse(jpeg, len, copy != 0, &d, flags);
@@ -670,6 +670,11 @@ uint32_t compeg_image_height(const compeg_image *img)
 uint32_t compeg_image_parallelism(const compeg_image *img)
 {
     return img ? img->data->metadata.total_restart_intervals : 0;
+}
+
+uint32_t compeg_image_components(const compeg_image *img)
+{
+    return img ? img->data->components : 0;
 }
 
 const uint8_t *compeg_image_metadata(const compeg_image *img)

@@ -33,6 +33,8 @@ void fill_desc(const ImageData &img, ImageDesc &d)
     d.mcu_h = md.max_vsample * 8;
     d.total_dus = img.total_dus();
     uint32_t k = 0;
+    // (a grayscale image: components 1 and 2 are all zero in the block -- no data units, hsample = vsample = 0, which
+    // the generic composite reads as "the neutral sample"; one data unit per MCU, 8 x 8 MCUs)
     for (uint32_t c = 0; c < 3; c++) {
         const Component &cm = md.components[c];
         d.du_base[c] = k;

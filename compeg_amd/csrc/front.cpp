@@ -320,6 +320,7 @@ Status ImageData::parse(const uint8_t *jpeg, size_t len, bool copy, ImageData **
     uint8_t frame_ids[3] = {0, 0, 0}, hv[3] = {0, 0, 0}, tq[3] = {0, 0, 0};
     uint8_t td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
     unsigned frame_w = 0, frame_h = 0;
+    unsigned frame_ncomp = 0; // 3, or 1: a grayscale frame (COMPEG_PARSE_GRAYSCALE)
 
     for (;;) {
         // next marker: skip to an FF, the byte after it names the segment
@@ -406,31 +407,46 @@ Status ImageData::parse(const uint8_t *jpeg, size_t len, bool copy, ImageData **
                 return unsupported(fmt("sample precision of %u bits is not supported", precision));
             if (have_frame)
                 return unsupported("encountered multiple SOF markers");
-            if (ncomp != 3)
+            const bool gray = (flags & COMPEG_PARSE_GRAYSCALE) && ncomp == 1;
+            if (ncomp != 3 && !gray)
                 return unsupported(fmt(
                     "frame with %u components not supported (only 3 components are supported)",
                     ncomp));
             const uint8_t *c = jpeg + seg.at;
-            for (int i = 0; i < 3; i++) {
-                frame_ids[i] = c[i * 3];
-                hv[i] = c[i * 3 + 1];
-                tq[i] = c[i * 3 + 2];
+            if (gray) {
+                // A lone component's sampling factors say nothing (T.81 A.2.2: its scan is not interleaved, an MCU is
+                // one data unit): checked for being factors at all, then ignored.
+                const unsigned h = c[1] >> 4, v = c[1] & 15;
+                if (h < 1 || h > 4 || v < 1 || v > 4)
+                    return unsupported(fmt("invalid sampling factors %ux%u for the only component (1-4 are valid)", h, v));
+                if (c[2] > 3)
+                    return unsupported(fmt("invalid quantization table selection [%u] (only tables 0-3 are valid)", c[2]));
+                frame_ids[0] = c[0];
+                hv[0] = 0x11;
+                tq[0] = c[2];
+            } else {
+                for (int i = 0; i < 3; i++) {
+                    frame_ids[i] = c[i * 3];
+                    hv[i] = c[i * 3 + 1];
+                    tq[i] = c[i * 3 + 2];
+                }
+                if (tq[0] > 3 || tq[1] > 3 || tq[2] > 3)
+                    return unsupported(fmt(
+                        "invalid quantization table selection [%u,%u,%u] (only tables 0-3 are valid)",
+                        tq[0], tq[1], tq[2]));
+                const bool any_luma = (flags & COMPEG_PARSE_ANY_LUMA_SAMPLING) &&
+                                      (hv[0] == 0x11 || hv[0] == 0x21 || hv[0] == 0x12 || hv[0] == 0x22);
+                if (hv[0] != 0x21 && !any_luma)
+                    return unsupported(
+                        fmt("invalid sampling factors %ux%u for Y component (expected 2x1)",
+                            hv[0] >> 4, hv[0] & 15));
+                if (hv[1] != 0x11 || hv[2] != 0x11)
+                    return unsupported(
+                        fmt("invalid U/V sampling factors %ux%u and %ux%u (expected 1x1)", hv[1] >> 4,
+                            hv[1] & 15, hv[2] >> 4, hv[2] & 15));
             }
-            if (tq[0] > 3 || tq[1] > 3 || tq[2] > 3)
-                return unsupported(fmt(
-                    "invalid quantization table selection [%u,%u,%u] (only tables 0-3 are valid)",
-                    tq[0], tq[1], tq[2]));
-            const bool any_luma = (flags & COMPEG_PARSE_ANY_LUMA_SAMPLING) &&
-                                  (hv[0] == 0x11 || hv[0] == 0x21 || hv[0] == 0x12 || hv[0] == 0x22);
-            if (hv[0] != 0x21 && !any_luma)
-                return unsupported(
-                    fmt("invalid sampling factors %ux%u for Y component (expected 2x1)",
-                        hv[0] >> 4, hv[0] & 15));
-            if (hv[1] != 0x11 || hv[2] != 0x11)
-                return unsupported(
-                    fmt("invalid U/V sampling factors %ux%u and %ux%u (expected 1x1)", hv[1] >> 4,
-                        hv[1] & 15, hv[2] >> 4, hv[2] & 15));
             have_frame = true;
+            frame_ncomp = ncomp;
             frame_w = x;
             frame_h = y;
         } else if (marker == 0xda) { // file.rs:155-209, lib.rs:726-756
@@ -455,16 +471,23 @@ Status ImageData::parse(const uint8_t *jpeg, size_t len, bool copy, ImageData **
                 return unsupported("non-baseline scan header");
             if (!have_frame)
                 return unsupported("SOS not preceded by SOF header");
-            if (ncomp != 3)
+            if (frame_ncomp == 1) {
+                if (ncomp != 1)
+                    return unsupported(fmt(
+                        "scan with %u components not supported (the frame has 1 component)", ncomp));
+                if (c[0] != frame_ids[0])
+                    return unsupported(fmt("scan component index mismatch (expected component [%u], got [%u])",
+                                           frame_ids[0], c[0]));
+            } else if (ncomp != 3)
                 return unsupported(fmt(
                     "scan with %u components not supported (only 3 components are supported)",
                     ncomp));
-            if (c[0] != frame_ids[0] || c[2] != frame_ids[1] || c[4] != frame_ids[2])
+            else if (c[0] != frame_ids[0] || c[2] != frame_ids[1] || c[4] != frame_ids[2])
                 return unsupported(
                     fmt("scan component index mismatch (expected component order [%u, %u, %u], "
                         "got [%u, %u, %u])",
                         frame_ids[0], frame_ids[1], frame_ids[2], c[0], c[2], c[4]));
-            for (int i = 0; i < 3; i++) {
+            for (unsigned i = 0; i < frame_ncomp; i++) {
                 td[i] = c[i * 2 + 1] >> 4;
                 ta[i] = c[i * 2 + 1] & 15;
             }
@@ -510,7 +533,7 @@ Status ImageData::parse(const uint8_t *jpeg, size_t len, bool copy, ImageData **
     // 2, 1, 4 for the only layout the reference accepts (Y 2x1, Cb/Cr 1x1)
     md.max_hsample = hv[0] >> 4;
     md.max_vsample = hv[0] & 15;
-    md.dus_per_mcu = md.max_hsample * md.max_vsample + 2;
+    md.dus_per_mcu = md.max_hsample * md.max_vsample + (frame_ncomp == 1 ? 0 : 2); // (grayscale: 1 x 1, one data unit)
     const uint32_t width_dus = (frame_w + 7) / 8, height_dus = (frame_h + 7) / 8;
     md.width_mcus = (width_dus + md.max_hsample - 1) / md.max_hsample;
     const uint32_t height_mcus = (height_dus + md.max_vsample - 1) / md.max_vsample;
@@ -522,7 +545,7 @@ Status ImageData::parse(const uint8_t *jpeg, size_t len, bool copy, ImageData **
     if (md.total_restart_intervals > kMaxRestartIntervals)
         return unsupported(fmt("number of restart intervals exceeds limit (%u > %u)",
                                md.total_restart_intervals, kMaxRestartIntervals));
-    for (int i = 0; i < 3; i++) {
+    for (unsigned i = 0; i < frame_ncomp; i++) { // (grayscale: components 1 and 2 stay all zero)
         md.components[i].hsample = hv[i] >> 4;
         md.components[i].vsample = hv[i] & 15;
         md.components[i].qtable = tq[i];
@@ -532,6 +555,7 @@ Status ImageData::parse(const uint8_t *jpeg, size_t len, bool copy, ImageData **
     md.retained_coefficients = kRetainedCoefficients;
     img->width = frame_w;
     img->height = frame_h;
+    img->components = frame_ncomp;
 
     // Concatenate the four LUTs: [Th0 DC, Th0 AC, Th1 DC, Th1 AC]; delegates
     // of later tables are rebased by the L2 entries in front (huffman.rs:247-271).

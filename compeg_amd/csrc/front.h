@@ -80,6 +80,9 @@ struct ImageData {
     // The EXIF orientation tag (1..8; 1: no usable tag) of the first APP1 "Exif" segment in front of the scan.  It never
     // changes what parse() accepts, rejects or says.
     uint32_t orientation = 1;
+    // Components of the frame: 3, or 1 -- a grayscale image (COMPEG_PARSE_GRAYSCALE): one 8x8 data unit per MCU, the
+    // metadata block's components 1 and 2 all zero.
+    uint32_t components = 3;
 
     const uint8_t *scan_data() const { return jpeg + scan_offset; }
     uint32_t total_mcus() const

@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "kernels_body.h"
+#include "gray_body.h"
 #include "coop_body.h"
 #include "walk_body.h"
 #include "kernels.h"
@@ -378,6 +379,7 @@ decode_fused_422_mcu_rec_kernel(const ImageDesc *__restrict__ descs, uint32_t l2
 // Extension layouts: decode_wave_fused_layout behind the plain prologue -- grid (workgroups per image,
 // images), no resident waves: inside the larger body above these kernels spill (4:2:0: 356 registers), alone they
 // do not (134 / 152 / 186 VGPRs).  Luma 1x1 (4:4:4), 1x2 (4:4:0) ...
+// (VS = 0: no chroma -- a grayscale image's one data unit an MCU, decode_wave_fused_gray)
 template <int HS, int VS, int MC>
 __device__ __forceinline__ void fused_layout_kernel_body(const ImageDesc *__restrict__ descs, uint32_t l2_in_lds, uint32_t window_words)
 {
@@ -408,7 +410,10 @@ __device__ __forceinline__ void fused_layout_kernel_body(const ImageDesc *__rest
     s.win_base = win_base;
     s.win_len = win_len;
     s.du_slots = reinterpret_cast<uint8_t *>(win) + align16(window_words * 4u);
-    decode_wave_fused_layout<HS, VS, MC>(d, s, wave_first + lane, lane);
+    if constexpr (VS == 0)
+        decode_wave_fused_gray<MC>(d, s, wave_first + lane, lane);
+    else
+        decode_wave_fused_layout<HS, VS, MC>(d, s, wave_first + lane, lane);
 }
 
 // (4:4:4 and 4:4:0: MCUs in pairs -- rows of 64 bytes; the last MCU of an odd restart interval alone -- from two MCUs an interval on: two waves to a SIMD;
@@ -438,6 +443,19 @@ __global__ void __launch_bounds__(512)
 decode_fused_420_kernel(const ImageDesc *__restrict__ descs, uint32_t l2_in_lds, uint32_t window_words)
 {
     fused_layout_kernel_body<2, 2, 1>(descs, l2_in_lds, window_words);
+}
+
+// ... and grayscale images (gray_body.h: one data unit an MCU, 16 or 32 sample registers a lane): pairs from two MCUs an
+// interval on, singly otherwise; three waves to a SIMD either way.
+__global__ void __launch_bounds__(768)
+decode_fused_gray_kernel(const ImageDesc *__restrict__ descs, uint32_t l2_in_lds, uint32_t window_words)
+{
+    fused_layout_kernel_body<1, 0, 2>(descs, l2_in_lds, window_words);
+}
+__global__ void __launch_bounds__(768)
+decode_fused_gray_single_kernel(const ImageDesc *__restrict__ descs, uint32_t l2_in_lds, uint32_t window_words)
+{
+    fused_layout_kernel_body<1, 0, 1>(descs, l2_in_lds, window_words);
 }
 
 // The batch kernel for restart intervals too long for whole-interval windows (decode_wave_fused_422_stream: `rows`
@@ -796,7 +814,8 @@ constexpr uint32_t kMaxWavesSplit = 16; // entropy_kernel: 4 per SIMD
 // 4:4:4 / 4:4:0: 1.095 / 0.864 ms per launch against 1.144 / 0.896 with one workgroup of eight; three or five waves,
 // i.e. nine or ten per CU, are slower than either, and so are twelve -- three workgroups of four with streamed windows:
 // 1.40 / 1.09 ms).
-uint32_t fused_layout_wave_cap(uint32_t hs, uint32_t vs, bool pairs) { return hs == 2 && vs == 2 ? 8u : (hs == 1 && pairs ? 4u : 12u); }
+// Grayscale (vs = 0): twelve, singly or in pairs -- its registers allow three waves per SIMD.
+uint32_t fused_layout_wave_cap(uint32_t hs, uint32_t vs, bool pairs) { return hs == 2 && vs == 2 ? 8u : (hs == 1 && vs != 0 && pairs ? 4u : 12u); }
 
 HuffLdsPlan plan_huffman(uint32_t max_intervals, uint32_t images, uint32_t max_l2,
                          uint32_t max_wave_words, bool fused, uint32_t wave_cap)
@@ -903,6 +922,7 @@ hipError_t launch_fused_layout(const ImageDesc *descs, uint32_t images, uint32_t
     const Kernel kernel = hs == 1 && vs == 1   ? (pairs ? decode_fused_444_kernel : decode_fused_444_single_kernel)
                           : hs == 1 && vs == 2 ? (pairs ? decode_fused_440_kernel : decode_fused_440_single_kernel)
                           : hs == 2 && vs == 2 ? decode_fused_420_kernel
+                          : hs == 1 && vs == 0 ? (pairs ? decode_fused_gray_kernel : decode_fused_gray_single_kernel)
                                                : nullptr;
     if (!kernel || plan.waves_per_block > fused_layout_wave_cap(hs, vs, pairs))
         return hipErrorInvalidValue;

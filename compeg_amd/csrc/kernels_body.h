@@ -1698,6 +1698,10 @@ CG_DEV void composite_generic_4px(const ImageDesc &d, uint32_t x0, uint32_t y, c
 #pragma unroll
     for (uint32_t c = 0; c < 3; c++) {
         const uint32_t hs = d.hsample[c], vs = d.vsample[c]; // 1 or 2
+        if (hs == 0u) { // (a grayscale image has no such component: the neutral sample, no load)
+            val[c] = 0x80808080u;
+            continue;
+        }
         const uint32_t xsh = (wsh - 3u) - (hs - 1u), ysh = (hsh - 3u) - (vs - 1u); // log2 of xscale, yscale
         const uint32_t yy = (row >> ysh) & 7u;
         const uint32_t du = d.du_base[c] + ((row * vs) >> hsh) * hs + ((col * hs) >> wsh);

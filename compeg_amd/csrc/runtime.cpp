@@ -196,8 +196,10 @@ bool use_stream_kernel(const HuffLdsPlan &plan, uint32_t max_intervals, uint32_t
 
 // The extension layouts' kernels: waves a CU holds (their registers: two to a SIMD) and the most a workgroup has
 // (fused_layout_wave_cap); a streamed form exists for 4:2:0 and for 4:4:4 / 4:4:0 with restart intervals of two MCUs or more.
+// Grayscale images (vs = 0: kernels.h) have none: their whole-window form takes every interval length, with global reads
+// beyond the window cap.
 constexpr uint32_t kLayoutCuWaves = 8;
-bool layout_has_stream_kernel(uint32_t hs, uint32_t vs, bool pairs) { return (hs == 2 && vs == 2) || (hs == 1 && pairs); }
+bool layout_has_stream_kernel(uint32_t hs, uint32_t vs, bool pairs) { return (hs == 2 && vs == 2) || (hs == 1 && vs != 0 && pairs); }
 
 bool use_coop_kernel(uint32_t max_intervals, uint32_t images, uint32_t restart_interval)
 {
@@ -277,6 +279,12 @@ void pinned_free(void *p) { (void)hipHostFree(p); }
 bool is_422(const ImageData &img)
 {
     return img.metadata.max_hsample == 2 && img.metadata.max_vsample == 1;
+}
+
+// An image's layout as the layouts' launchers name it (kernels.h): the luma sampling, 1 x 0 for a grayscale image.
+uint32_t layout_vs(const ImageData &img)
+{
+    return img.components == 1 ? 0u : img.metadata.components[0].vsample;
 }
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -860,7 +868,7 @@ Status compeg_decoder::enqueue(const ImageData &img, hipStream_t stream, bool *c
                                                     md.total_restart_intervals);
     const bool fused = use_fused_pipeline() && is_422(img);
     // (the extension pipeline's first kernel carries the IDCT: planned like the fused kernel)
-    const uint32_t luma_h = md.components[0].hsample, luma_v = md.components[0].vsample;
+    const uint32_t luma_h = md.components[0].hsample, luma_v = layout_vs(img);
     // (8-pixel MCUs in pairs: rows of 64 bytes; of an odd interval the last MCU alone.  Intervals of one MCU: the single form)
     const bool mcu_pairs = luma_h == 1 && md.restart_interval >= 2u;
     const HuffLdsPlan plan = plan_huffman(md.total_restart_intervals, 1, staged_lut_entries(img), span,
@@ -1136,10 +1144,15 @@ bool peek_item(const uint8_t *j, size_t len, unsigned flags, UploadItem &it)
             h = (uint32_t(d[1]) << 8) | d[2];
             w = (uint32_t(d[3]) << 8) | d[4];
             comps = d[5];
-            if (comps != 3 || seg < 8 + 3 * comps)
+            if ((comps != 3 && !(comps == 1 && (flags & COMPEG_PARSE_GRAYSCALE))) || seg < 8 + 3 * comps)
                 return false;
             hs = d[7] >> 4;
             vs = d[7] & 15;
+            if (comps == 1) { // (a lone component's factors are ignored: an MCU is one data unit)
+                if (hs < 1 || hs > 4 || vs < 1 || vs > 4)
+                    return false;
+                hs = vs = 1;
+            }
         } else if (m == 0xdd) {
             if (seg < 4)
                 return false;
@@ -1147,8 +1160,8 @@ bool peek_item(const uint8_t *j, size_t len, unsigned flags, UploadItem &it)
         } else if (m == 0xda) {
             if (!sof || w == 0 || h == 0)
                 return false;
-            const bool ok422 = hs == 2 && vs == 1;
-            if (!ok422 && !(flags & COMPEG_PARSE_ANY_LUMA_SAMPLING))
+            const bool ok422 = comps == 3 && hs == 2 && vs == 1;
+            if (!ok422 && comps == 3 && !(flags & COMPEG_PARSE_ANY_LUMA_SAMPLING))
                 return false;
             if (hs < 1 || hs > 2 || vs < 1 || vs > 2)
                 return false;
@@ -1160,7 +1173,7 @@ bool peek_item(const uint8_t *j, size_t len, unsigned flags, UploadItem &it)
             it.width = w;
             it.height = h;
             it.intervals = uint32_t(mcus / r);
-            it.total_dus = uint32_t(it.intervals * r * (hs * vs + 2));
+            it.total_dus = uint32_t(it.intervals * r * (hs * vs + (comps == 1 ? 0 : 2)));
             it.is422 = ok422;
             it.covered = uint64_t(it.intervals) * r >= mcus;
             // five LUT sections at their largest: L1, an L2 LUT of 32767 entries, the direct tables
@@ -1197,7 +1210,7 @@ void compeg_batch::note_batch_properties(const ImageData *const *images, size_t 
 {
     generic_layout = false;
     layout_h = n ? images[0]->metadata.components[0].hsample : 0;
-    layout_v = n ? images[0]->metadata.components[0].vsample : 0;
+    layout_v = n ? layout_vs(*images[0]) : 0;
     layout_pairs = true;
     one_mcu_intervals = n > 0;
     min_restart_interval = n ? 0xffffffffu : 0u;
@@ -1224,7 +1237,7 @@ void compeg_batch::note_batch_properties(const ImageData *const *images, size_t 
         const ImageData &img = *images[i], &first = *images[0];
         orientations[i] = img.orientation;
         generic_layout = generic_layout || !is_422(img);
-        if (img.metadata.components[0].hsample != layout_h || img.metadata.components[0].vsample != layout_v)
+        if (img.metadata.components[0].hsample != layout_h || layout_vs(img) != layout_v)
             layout_h = layout_v = 0; // (mixed samplings in one batch)
         layout_pairs = layout_pairs && img.metadata.restart_interval >= 2u;
         one_mcu_intervals = one_mcu_intervals && img.metadata.restart_interval == 1u;

@@ -196,7 +196,7 @@ struct compeg_batch {
     uint32_t max_intervals = 0, max_dus = 0, max_l2 = 0, max_span = 0;
     // some image is not 4:2:2 (extension): the whole batch takes the three-kernel pipeline
     bool generic_layout = false;
-    uint32_t layout_h = 0, layout_v = 0; // luma sampling all images share (0: they differ)
+    uint32_t layout_h = 0, layout_v = 0; // luma sampling all images share (0: they differ; 1 x 0: grayscale images -- kernels.h)
     bool layout_pairs = false;           // ... and every restart interval holds two MCUs or more (8-pixel MCUs in pairs)
     bool one_mcu_intervals = false;      // every restart interval is one MCU
     uint32_t stream_mcu_words = 0;       // the batch's average MCU in stream words, rounded up (plan_stream)

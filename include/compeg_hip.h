@@ -96,11 +96,23 @@ int compeg_image_parse(const uint8_t *jpeg, size_t len, int copy, compeg_image *
  * colour conversion) stays the reference's.  On valid streams the output then
  * no longer depends on the restart interval. */
 #define COMPEG_PARSE_STANDARD_ENTROPY 2u
+/* COMPEG_PARSE_GRAYSCALE: baseline frames with one component are accepted too
+ * (the reference rejects them, lib.rs:640-672).  The lone component's sampling
+ * factors (1..4 each) are ignored as T.81 A.2.2 has it: an MCU is one 8x8 data
+ * unit, the image ceil(X/8) x ceil(Y/8) of them.  Such an image decodes to
+ * what its 4:4:4 twin decodes to -- the same file with Cb = Cr = 128
+ * throughout --: R = G = B = the luma sample, A = 255; retained coefficients,
+ * entropy quirks and the transform are those of every other image.  Its
+ * Metadata block describes component 0 as 1x1 and leaves components 1 and 2
+ * zero, with max_hsample = max_vsample = dus_per_mcu = 1. */
+#define COMPEG_PARSE_GRAYSCALE 4u
 int compeg_image_parse_ext(const uint8_t *jpeg, size_t len, int copy, unsigned flags, compeg_image **out);
 void compeg_image_free(compeg_image *img);
 uint32_t compeg_image_width(const compeg_image *img);       /* lib.rs:828-831 */
 uint32_t compeg_image_height(const compeg_image *img);      /* lib.rs:834-837 */
 uint32_t compeg_image_parallelism(const compeg_image *img); /* lib.rs:838-846 */
+/* Extension: components of the frame -- 3, or 1 for a grayscale image (COMPEG_PARSE_GRAYSCALE). */
+uint32_t compeg_image_components(const compeg_image *img);
 /* What the reference uploads per image (src/lib.rs:397-407), exposed so that a
  * binding's tests can compare them byte for byte: the 1112-byte Metadata
  * block, the 2048-byte L1 LUT, the L2 LUT, and the location of the
@@ -175,7 +187,7 @@ int compeg_decoder_last_stage_times(const compeg_decoder *dec, compeg_stage_time
 #define COMPEG_KERNEL_COOP_TEAM 3  /* decode_coop_team_422_kernel: the lanes of a team work inside the intervals */
 #define COMPEG_KERNEL_GENERIC 4    /* entropy_samples_kernel + composite_generic_kernel (batches of mixed layouts) */
 #define COMPEG_KERNEL_SPLIT 5      /* entropy_kernel + idct_composite_kernel (development pipeline) */
-#define COMPEG_KERNEL_FUSED_LAYOUT 6 /* decode_fused_444 / _440 / _420_kernel (one layout other than 4:2:2) */
+#define COMPEG_KERNEL_FUSED_LAYOUT 6 /* decode_fused_444 / _440 / _420 / _gray_kernel (one layout other than 4:2:2; grayscale images) */
 #define COMPEG_KERNEL_FUSED_STREAM 7 /* decode_fused_422 / _444 / _440 / _420_stream_kernel: the batch kernels with streamed
                                        windows (long restart intervals, dense streams) */
 #define COMPEG_KERNEL_WALK_MCU 8     /* walk_mcus_422_kernel + decode_fused_422_mcu_rec_kernel: a lane per restart interval

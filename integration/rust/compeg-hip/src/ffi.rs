@@ -103,6 +103,7 @@ pub const COMPEG_E_COUNT_MISMATCH: c_int = -4;
 pub const COMPEG_E_HIP: c_int = -5;
 pub const COMPEG_PARSE_ANY_LUMA_SAMPLING: c_uint = 1;
 pub const COMPEG_PARSE_STANDARD_ENTROPY: c_uint = 2;
+pub const COMPEG_PARSE_GRAYSCALE: c_uint = 4;
 pub const COMPEG_KERNEL_NONE: c_int = 0;
 pub const COMPEG_KERNEL_FUSED: c_int = 1;
 pub const COMPEG_KERNEL_PAIR: c_int = 2;
@@ -151,6 +152,7 @@ extern "C" {
     pub fn compeg_image_width(img: *const compeg_image) -> u32;
     pub fn compeg_image_height(img: *const compeg_image) -> u32;
     pub fn compeg_image_parallelism(img: *const compeg_image) -> u32;
+    pub fn compeg_image_components(img: *const compeg_image) -> u32;
     pub fn compeg_image_metadata(img: *const compeg_image) -> *const u8;
     pub fn compeg_image_huffman_l1(img: *const compeg_image) -> *const u8;
     pub fn compeg_image_huffman_l2(img: *const compeg_image, nbytes: *mut usize) -> *const u8;

@@ -391,6 +391,8 @@ pub struct ParseFlags {
     pub any_luma_sampling: bool,
     /// Bit reader topped up in front of DC codes, ZRL = 16 positions (ITU-T T.81).
     pub standard_entropy: bool,
+    /// Frames with one component are accepted: R = G = B = the luma sample.
+    pub grayscale: bool,
 }
 
 /// A parsed and validated JPEG (baseline, 8 bit, YCbCr 4:2:2, restart intervals).
@@ -414,7 +416,7 @@ impl<'a> ImageData<'a> {
 
     /// Extension: like `new`, but 4:4:4, 4:4:0 and 4:2:0 are accepted as well as 4:2:2.
     pub fn new_any_sampling(jpeg: impl Into<Cow<'a, [u8]>>) -> Result<Self> {
-        Self::with_flags(jpeg, ParseFlags { any_luma_sampling: true, standard_entropy: false })
+        Self::with_flags(jpeg, ParseFlags { any_luma_sampling: true, ..ParseFlags::default() })
     }
 
     /// Extension: `ParseFlags` widen the accepted subset / switch the entropy decoder to ITU-T T.81
@@ -423,7 +425,8 @@ impl<'a> ImageData<'a> {
         let jpeg = jpeg.into();
         let mut raw = ptr::null_mut();
         let bits = if flags.any_luma_sampling { ffi::COMPEG_PARSE_ANY_LUMA_SAMPLING } else { 0 }
-            | if flags.standard_entropy { ffi::COMPEG_PARSE_STANDARD_ENTROPY } else { 0 };
+            | if flags.standard_entropy { ffi::COMPEG_PARSE_STANDARD_ENTROPY } else { 0 }
+            | if flags.grayscale { ffi::COMPEG_PARSE_GRAYSCALE } else { 0 };
         check(unsafe { ffi::compeg_image_parse_ext(jpeg.as_ptr(), jpeg.len(), 0, bits, &mut raw) })?;
         Ok(ImageData { raw: NonNull::new(raw).expect("compeg_image_parse_ext returned null"), _jpeg: jpeg })
     }
@@ -439,6 +442,11 @@ impl<'a> ImageData<'a> {
     /// Number of restart intervals = lanes that decode in parallel.
     pub fn parallelism(&self) -> u32 {
         unsafe { ffi::compeg_image_parallelism(self.raw.as_ptr()) }
+    }
+
+    /// Extension: components of the frame -- 3, or 1 for a grayscale image (`ParseFlags::grayscale`).
+    pub fn components(&self) -> u32 {
+        unsafe { ffi::compeg_image_components(self.raw.as_ptr()) }
     }
 
     /// Extension: the file's EXIF orientation tag, 1..8; 1 where it has no usable one.
