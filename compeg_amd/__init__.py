@@ -18,14 +18,15 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
-                   LIB_PATH, METADATA_BYTES, Error, FilterSpec, NhwcSpec, OrientedRegion, Rect, Region, ResizeSpec, TensorSpec, check,
+                   LIB_PATH, METADATA_BYTES, Error, FilterSpec, LumaSpec, NhwcSpec, OrientedRegion, Rect, Region, ResizeSpec, TensorSpec, check,
                    lib)
 
 __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Texture", "Error", "HostBuffer", "JpegList",
            "host_register", "host_unregister", "version", "LIB_PATH", "tensor_shape", "TENSOR_DTYPES", "TENSOR_ORDERS",
            "resized_tensor_shape", "RESIZE_FILTERS", "ResizeSpec", "Rect", "Region", "FIT_ALIGNS", "region_fit",
            "region_tensor_shape", "FILTER_KERNELS", "FilterSpec", "filtered_tensor_shape", "ORIENTATIONS", "OrientedRegion",
-           "orient_rect", "oriented_tensor_shape", "NhwcSpec", "nhwc_tensor_shape"]
+           "orient_rect", "oriented_tensor_shape", "NhwcSpec", "nhwc_tensor_shape", "LumaSpec", "LUMA_WEIGHTS",
+           "luma_tensor_shape"]
 
 
 # compeg_decoder_last_kernel / compeg_batch_last_kernel (include/compeg_hip.h: COMPEG_KERNEL_*)
@@ -314,6 +315,93 @@ def _nhwc_device_range(dst, size, channels):
                     ("planar memory -- give it channels-last strides (torch: memory_format=torch.channels_last)" if planar else
                      f"neither [.., {oh}, {ow}, {channels}] row-major nor [.., {channels}, {oh}, {ow}] with channels-last strides"))
     return address, below * itemsize
+
+
+# Luma tensor output (include/compeg_hip.h: compeg_luma_spec): the weights of R, G and B by name, in 1/65536
+LUMA_WEIGHTS = {"bt601": (19595, 38470, 7471), "bt709": (13933, 46871, 4732), "r": (65536, 0, 0), "g": (0, 65536, 0), "b": (0, 0, 65536)}
+
+
+def _luma_spec(weights):
+    """compeg_luma_spec from a name of LUMA_WEIGHTS or three integers (which the library checks)."""
+    if isinstance(weights, LumaSpec):
+        return weights
+    if isinstance(weights, str):
+        if weights not in LUMA_WEIGHTS:
+            raise Error(f"unknown luma weights {weights!r} (one of {', '.join(LUMA_WEIGHTS)}, or three integers with a sum of 65536)")
+        weights = LUMA_WEIGHTS[weights]
+    weights = tuple(weights)
+    if len(weights) != 3 or any(int(w) != w or not 0 <= w <= 0xffffffff for w in weights):
+        raise Error(f"luma weights {weights!r} are not three integers (each 0..65536, their sum 65536)")
+    spec = LumaSpec()
+    spec.weights[:] = [int(w) for w in weights]
+    spec.reserved = 0
+    return spec
+
+
+def _luma_pad(pad):
+    return C.pointer(C.c_float(float(pad))) if pad is not None else None
+
+
+def luma_tensor_shape(width, height, size, region=None, orientation=1, weights="bt601", kernel="bicubic", dtype="f16", downscale=1):
+    """((1, oh, ow), bytes, (ph, pw)) of one slot of a luma pack: oriented_tensor_shape for pack_tensor_luma, one channel
+    a slot (compeg_luma_tensor_shape; no device needed)."""
+    spec = _tensor_spec(dtype, downscale, (1, 1, 1), (0, 0, 0), "rgb")
+    filter = _filter_spec(size, kernel)
+    luma = _luma_spec(weights)
+    list_, _ = _oriented_regions([region if region is not None else (0, None, None)], orientation)
+    pw, ph, nbytes = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    check(lib.compeg_luma_tensor_shape(C.byref(spec), C.byref(filter), C.byref(luma), width, height, list_, C.byref(pw), C.byref(ph), C.byref(nbytes)))
+    return (1, filter.out_height, filter.out_width), nbytes.value, (ph.value, pw.value)
+
+
+def _luma_device_range(dst, size, count):
+    """(address, bytes) of a luma pack destination of `count` slots of size = (ow, oh): _device_range's forms, with a tensor
+    taken by its shape and strides -- it must cover its memory densely, in row-major order, be [.., 1, oh, ow],
+    [.., oh, ow, 1] or [.., oh, ow], and hold `count` slots: [N, 3, oh, ow] is 3 N slots, so a three-channel tensor, like a
+    slice or another extent, is an error here, not a scrambled image.  No framework is imported for it."""
+    if isinstance(dst, tuple) and len(dst) == 2:
+        return int(dst[0]), int(dst[1])
+    if hasattr(dst, "data_ptr") and hasattr(dst, "stride") and hasattr(dst, "shape") and hasattr(dst, "element_size"):
+        address, itemsize = int(dst.data_ptr()), int(dst.element_size())
+        shape, strides = tuple(int(n) for n in dst.shape), tuple(int(n) for n in dst.stride())
+    else:
+        cai = getattr(dst, "__cuda_array_interface__", None)
+        if cai is None:
+            raise Error("pack_tensor_luma: dst is neither (address, nbytes), a tensor, nor a __cuda_array_interface__ object")
+        address, itemsize = int(cai["data"][0]), np.dtype(cai["typestr"]).itemsize
+        shape = tuple(int(n) for n in cai["shape"])
+        if cai.get("strides") is None:
+            strides = tuple(int(np.prod(shape[i + 1:], dtype=np.int64)) for i in range(len(shape)))
+        else:
+            if any(int(b) % itemsize for b in cai["strides"]):
+                raise Error("pack_tensor_luma: the destination's strides are no multiples of its element size")
+            strides = tuple(int(b) // itemsize for b in cai["strides"])
+    ow, oh = size
+    what = f"shape {shape} with strides {strides}"
+    forms = f"[.., 1, {oh}, {ow}], [.., {oh}, {ow}, 1] or [.., {oh}, {ow}]"
+    if any(n < 1 for n in shape):
+        raise Error(f"pack_tensor_luma: the destination has {what}, none of {forms}")
+    # the slot's axes, whichever form names them; what is in front of them counts slots
+    if len(shape) >= 3 and shape[-3:] == (1, oh, ow):
+        lead = shape[:-3]
+    elif len(shape) >= 3 and shape[-3:] == (oh, ow, 1):
+        lead = shape[:-3]
+    elif len(shape) >= 2 and shape[-2:] == (oh, ow):
+        lead = shape[:-2]
+    else:
+        raise Error(f"pack_tensor_luma: the destination has {what}, none of {forms} (one channel a slot)")
+    # row-major and dense: an axis's stride is the extent of the axes behind it (an axis of 1: any stride)
+    below = 1
+    for n, stride in zip(reversed(shape), reversed(strides)):
+        if n != 1 and stride != below:
+            raise Error(f"pack_tensor_luma: the destination ({what}) does not cover its memory densely in row-major order "
+                        "(a slice, an expanded or a permuted view)")
+        below *= n
+    slots = int(np.prod(lead, dtype=np.int64))
+    if slots != count:
+        raise Error(f"pack_tensor_luma: the destination ({what}) holds {slots} slots of one channel, the call packs {count} "
+                    "(a luma pack writes one channel a slot: no three-channel tensor)")
+    return address, slots * oh * ow * itemsize
 
 
 def _host_view(data):
@@ -702,6 +790,21 @@ class Decoder:
         check(lib.compeg_decoder_pack_tensor_nhwc(self._h, C.byref(spec), C.byref(filter), C.byref(nhwc), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
                                                   C.c_void_p(hip_stream)))
 
+    def pack_tensor_luma(self, dst, size, regions=None, orientation="exif", weights="bt601", kernel="bicubic", pad=0.0, dtype="f16", downscale=1,
+                         scale=1.0, bias=0.0, hip_stream=0):
+        """Extension (compeg_decoder_pack_tensor_luma): pack_tensor_oriented with one channel a slot, [count, 1, oh, ow]: per
+        source pixel L = (wR R + wG G + wB B + 32768) >> 16, resampled like a channel of the oriented pack.  weights: "bt601"
+        (PIL's convert("L")), "bt709", "r", "g", "b", or three integers with a sum of 65536; a grayscale frame gives its own
+        values under any of them.  pad, scale, bias: one number each.  dst: (address, nbytes), or a dense tensor of `count`
+        slots, [.., 1, oh, ow], [.., oh, ow, 1] or [.., oh, ow].  Returns without waiting."""
+        spec = _tensor_spec(dtype, downscale, (scale,) * 3, (bias,) * 3, "rgb")
+        filter = _filter_spec(size, kernel)
+        luma = _luma_spec(weights)
+        list_, n = _oriented_regions(regions if regions is not None else [(0, None, None)], orientation)
+        addr, nbytes = _luma_device_range(dst, size, n)
+        check(lib.compeg_decoder_pack_tensor_luma(self._h, C.byref(spec), C.byref(filter), C.byref(luma), list_, n, _luma_pad(pad), C.c_void_p(addr),
+                                                  nbytes, C.c_void_p(hip_stream)))
+
     def read_coefficients(self, total_dus):
         out = np.empty(total_dus * 32, dtype=np.int32)
         check(lib.compeg_decoder_read_coefficients(self._h, out.ctypes.data, out.size))
@@ -856,6 +959,19 @@ class Batch:
         addr, nbytes = _nhwc_device_range(dst, size, channels)
         check(lib.compeg_batch_pack_tensor_nhwc(self._h, C.byref(spec), C.byref(filter), C.byref(nhwc), list_, n, _pad(pad), C.c_void_p(addr), nbytes,
                                                 C.c_void_p(hip_stream)))
+
+    def pack_tensor_luma(self, dst, size, regions=None, orientation="exif", weights="bt601", kernel="bicubic", pad=0.0, dtype="f16", downscale=1,
+                         scale=1.0, bias=0.0, hip_stream=0):
+        """Extension (compeg_batch_pack_tensor_luma): Decoder.pack_tensor_luma over the last decode's images, regions as in
+        pack_tensor_oriented.  regions=None: every image, whole, into its own upright slot, [count, 1, oh, ow].  Returns
+        without waiting; wait() covers it."""
+        spec = _tensor_spec(dtype, downscale, (scale,) * 3, (bias,) * 3, "rgb")
+        filter = _filter_spec(size, kernel)
+        luma = _luma_spec(weights)
+        list_, n = _oriented_regions(regions if regions is not None else [(i, None, None) for i in range(self.count())], orientation)
+        addr, nbytes = _luma_device_range(dst, size, n)
+        check(lib.compeg_batch_pack_tensor_luma(self._h, C.byref(spec), C.byref(filter), C.byref(luma), list_, n, _luma_pad(pad), C.c_void_p(addr),
+                                                nbytes, C.c_void_p(hip_stream)))
 
     def orientation(self, index):
         """The EXIF orientation tag (1..8) of image `index` of the last upload (compeg_batch_image_orientation)."""

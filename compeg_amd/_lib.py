@@ -61,6 +61,11 @@ class NhwcSpec(C.Structure):
     _fields_ = [("channels", C.c_uint32), ("fill", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class LumaSpec(C.Structure):
+    """compeg_luma_spec (include/compeg_hip.h, "Luma tensor output"): the weights of R, G and B in 1/65536, their sum 65536."""
+    _fields_ = [("weights", C.c_uint32 * 3), ("reserved", C.c_uint32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -160,6 +165,9 @@ def _load():
         "compeg_nhwc_tensor_shape": (i, [C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(NhwcSpec), u32, u32, C.POINTER(OrientedRegion), pu32, pu32, psz]),
         "compeg_decoder_pack_tensor_nhwc": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(NhwcSpec), C.POINTER(OrientedRegion), sz, C.POINTER(C.c_float), vp, sz, vp]),
         "compeg_batch_pack_tensor_nhwc": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(NhwcSpec), C.POINTER(OrientedRegion), sz, C.POINTER(C.c_float), vp, sz, vp]),
+        "compeg_luma_tensor_shape": (i, [C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(LumaSpec), u32, u32, C.POINTER(OrientedRegion), pu32, pu32, psz]),
+        "compeg_decoder_pack_tensor_luma": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(LumaSpec), C.POINTER(OrientedRegion), sz, C.POINTER(C.c_float), vp, sz, vp]),
+        "compeg_batch_pack_tensor_luma": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(LumaSpec), C.POINTER(OrientedRegion), sz, C.POINTER(C.c_float), vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("COMPEG_LIB") and not hasattr(L, name):

@@ -246,16 +246,18 @@ int check_region(const compeg_region *region, const compeg_tensor_spec *spec, co
     return COMPEG_OK;
 }
 
-// What every slot pack checks, behind its specs, before it looks at its object: the list and the pad.
-int check_slot_list(const void *regions, size_t count, const float *pad)
+// What every slot pack checks, behind its specs, before it looks at its object: the list and the pad's values (three by
+// source channel; the luma packs': one).
+int check_slot_list(const void *regions, size_t count, const float *pad, int pad_values)
 {
     if (!regions)
         return fail(COMPEG_E_INVALID_ARG, "tensor: regions is NULL");
     if (count == 0)
         return fail(COMPEG_E_INVALID_ARG, "tensor: a region count of 0");
-    for (int c = 0; pad && c < 3; c++)
+    for (int c = 0; pad && c < pad_values; c++)
         if (!std::isfinite(pad[c]))
-            return fail(COMPEG_E_INVALID_ARG, ("tensor: pad of channel " + std::to_string(c) + " is not finite").c_str());
+            return fail(COMPEG_E_INVALID_ARG, pad_values == 1 ? "tensor: pad is not finite"
+                                                              : ("tensor: pad of channel " + std::to_string(c) + " is not finite").c_str());
     return COMPEG_OK;
 }
 
@@ -353,6 +355,25 @@ int check_nhwc_spec(const compeg_nhwc_spec *nhwc)
     return COMPEG_OK;
 }
 
+// compeg_luma_spec as the header has it.
+int check_luma_spec(const compeg_luma_spec *luma)
+{
+    static const char *const names[] = {"R", "G", "B"};
+    if (!luma)
+        return fail(COMPEG_E_INVALID_ARG, "luma is NULL");
+    uint64_t sum = 0;
+    for (int c = 0; c < 3; c++) {
+        if (luma->weights[c] > 65536u)
+            return fail(COMPEG_E_INVALID_ARG, ("luma: weight " + std::to_string(luma->weights[c]) + " of " + names[c] + " is above 65536").c_str());
+        sum += luma->weights[c];
+    }
+    if (sum != 65536u)
+        return fail(COMPEG_E_INVALID_ARG, ("luma: the weights' sum " + std::to_string(sum) + " is not 65536").c_str());
+    if (luma->reserved != 0u)
+        return fail(COMPEG_E_INVALID_ARG, "luma: reserved must be 0");
+    return COMPEG_OK;
+}
+
 // What the *_tensor_shape calls end with: the prefiltered extent of the checked source rectangle and a slot's bytes.
 int shape_result(const compeg_rect &src, uint32_t k, size_t slot_bytes, uint32_t *pre_width, uint32_t *pre_height, size_t *bytes)
 {
@@ -418,11 +439,12 @@ struct SlotImage {
 const compeg_region &plain(const compeg_region &region) { return region; }
 const compeg_region &plain(const compeg_oriented_region &region) { return region.region; }
 
-// What a slot family -- region, filtered, oriented or channels-last tensor output -- adds to the two roads below: its
-// specs (the layout's on its own: a pack checks it behind the list), a slot's elements, its grid, its check of one
-// region and its pack.
+// What a slot family -- region, filtered, oriented, channels-last or luma tensor output -- adds to the two roads below: its
+// specs (the layout's on its own: a pack checks it behind the list), how many pad values it reads, a slot's elements,
+// its grid, its check of one region and its pack.
 struct RegionPack {
     using Region = compeg_region;
+    static constexpr int kPadValues = 3;
     const compeg_tensor_spec *spec;
     const compeg_resize_spec *resize;
     int check_specs(size_t *elem_bytes) const
@@ -447,6 +469,7 @@ struct RegionPack {
 
 struct FilterPack {
     using Region = compeg_region;
+    static constexpr int kPadValues = 3;
     const compeg_tensor_spec *spec;
     const compeg_filter_spec *filter;
     int check_specs(size_t *elem_bytes) const
@@ -473,6 +496,7 @@ struct FilterPack {
 // it, NULL included): one family, so that the two check the same things in the same order.
 struct OrientPack {
     using Region = compeg_oriented_region;
+    static constexpr int kPadValues = 3;
     const compeg_tensor_spec *spec;
     const compeg_filter_spec *filter;
     bool channels_last;
@@ -504,7 +528,32 @@ struct OrientPack {
     }
 };
 
-// compeg_{region,filtered,oriented,nhwc}_tensor_shape: the family's specs and its check of one region of a width x height
+// Luma tensor output: the oriented family's specs, grid and check of a region; one element a pixel, the weights for a
+// layout (luma as the caller gave it, NULL included), one pad value.
+struct LumaPack {
+    using Region = compeg_oriented_region;
+    static constexpr int kPadValues = 1;
+    const compeg_tensor_spec *spec;
+    const compeg_filter_spec *filter;
+    const compeg_luma_spec *luma;
+    OrientPack oriented() const { return OrientPack{spec, filter, false, nullptr}; }
+    int check_specs(size_t *elem_bytes) const { return oriented().check_specs(elem_bytes); }
+    int check_layout() const { return check_luma_spec(luma); }
+    size_t slot_elements() const { return size_t(filter->out_height) * size_t(filter->out_width); }
+    template <class Owner>
+    bool grid_fits(const Owner &owner, const Region *regions, size_t count) const { return oriented().grid_fits(owner, regions, count); }
+    int check_one(const Region *region, const SlotImage &image, const std::string &which, Region *out) const
+    {
+        return oriented().check_one(region, image, which, out);
+    }
+    template <class Owner>
+    Status pack(Owner &owner, const Region *list, size_t count, const float *pad, void *dst, hipStream_t stream) const
+    {
+        return owner.pack_tensor_luma(*spec, *filter, *luma, list, count, pad, dst, stream);
+    }
+};
+
+// compeg_{region,filtered,oriented,nhwc,luma}_tensor_shape: the family's specs and its check of one region of a width x height
 // image that carries no tag; then the prefiltered extent of the region's source and a slot's bytes.
 template <class Family>
 int slot_tensor_shape(const Family &family, const typename Family::Region *region, uint32_t width, uint32_t height, uint32_t *pre_width,
@@ -535,7 +584,7 @@ int pack_slot_tensor(Owner *owner, const Family &family, const typename Family::
         size_t elem = 0;
         int rc = family.check_specs(&elem);
         if (rc == COMPEG_OK)
-            rc = check_slot_list(regions, count, pad);
+            rc = check_slot_list(regions, count, pad, Family::kPadValues);
         if (rc == COMPEG_OK)
             rc = family.check_layout();
         if (rc != COMPEG_OK)
@@ -565,7 +614,9 @@ int pack_slot_tensor(Owner *owner, const Family &family, const typename Family::
             if (rc != COMPEG_OK)
                 return rc;
         }
-        const float pad_copy[3] = {pad ? pad[0] : 0.0f, pad ? pad[1] : 0.0f, pad ? pad[2] : 0.0f};
+        float pad_copy[3] = {0.0f, 0.0f, 0.0f};
+        for (int c = 0; pad && c < Family::kPadValues; c++)
+            pad_copy[c] = pad[c];
         Status s = family.pack(*owner, list.data(), count, pad_copy, device_dst, stream_of(*owner, hip_stream));
         return s.ok() ? ok() : fail(s);
     });
@@ -1711,6 +1762,29 @@ int compeg_batch_pack_tensor_nhwc(compeg_batch *batch, const compeg_tensor_spec 
                                   void *device_dst, size_t dst_bytes, void *hip_stream)
 {
     return pack_slot_tensor(batch, OrientPack{spec, filter, true, nhwc}, regions, count, pad, device_dst, dst_bytes, hip_stream);
+}
+
+/* ---- Luma tensor output ---------------------------------------------------- */
+
+int compeg_luma_tensor_shape(const compeg_tensor_spec *spec, const compeg_filter_spec *filter, const compeg_luma_spec *luma, uint32_t width,
+                             uint32_t height, const compeg_oriented_region *region, uint32_t *pre_width, uint32_t *pre_height,
+                             size_t *bytes_per_slot)
+{
+    return slot_tensor_shape(LumaPack{spec, filter, luma}, region, width, height, pre_width, pre_height, bytes_per_slot);
+}
+
+int compeg_decoder_pack_tensor_luma(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
+                                    const compeg_luma_spec *luma, const compeg_oriented_region *regions, size_t count, const float *pad,
+                                    void *device_dst, size_t dst_bytes, void *hip_stream)
+{
+    return pack_slot_tensor(dec, LumaPack{spec, filter, luma}, regions, count, pad, device_dst, dst_bytes, hip_stream);
+}
+
+int compeg_batch_pack_tensor_luma(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
+                                  const compeg_luma_spec *luma, const compeg_oriented_region *regions, size_t count, const float *pad,
+                                  void *device_dst, size_t dst_bytes, void *hip_stream)
+{
+    return pack_slot_tensor(batch, LumaPack{spec, filter, luma}, regions, count, pad, device_dst, dst_bytes, hip_stream);
 }
 
 } // extern "C"

@@ -187,6 +187,12 @@ hipError_t launch_nhwc_tensor(const void *device_blob, size_t tables_at, uint32_
                               const compeg_filter_spec &filter, const compeg_nhwc_spec &nhwc, bool upright, bool transposed, const float *pad,
                               void *dst, hipStream_t stream);
 
+// Luma tensor output (luma_kernels.hip, luma_body.h): the oriented pack's blob (make_orient_blob) and grid
+// (orient_grid_fits), one channel a slot, the weighted sum of R, G and B; dst: [slots][oh][ow]; pad: one value.
+hipError_t launch_luma_tensor(const void *device_blob, size_t tables_at, uint32_t slots, const compeg_tensor_spec &spec,
+                              const compeg_filter_spec &filter, const compeg_luma_spec &luma, bool upright, bool transposed, const float *pad,
+                              void *dst, hipStream_t stream);
+
 #if defined(CG_AC_STAMPS)
 // diagnostic build: AC-loop cycle counters (kernels_body.h)
 hipError_t read_ac_stamps(unsigned long long out[4], bool reset);

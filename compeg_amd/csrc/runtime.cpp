@@ -2441,9 +2441,9 @@ Status compeg_batch::pack_tensor_resized(const compeg_tensor_spec &spec, const c
     return send_resized(*this, records.data(), records.size(), 0, uint32_t(count), spec, resize, dst, stream);
 }
 
-// The slot families -- region, filtered, oriented and channels-last tensor output -- go down one road, pack_slots.  An
-// owner supplies where a region's image lies (and, above, its ordering); a family its grid test, its placement of a
-// slot, its blob, its launch and what it says when the blob could not be made.
+// The slot families -- region, filtered, oriented, channels-last and luma tensor output -- go down one road,
+// pack_slots.  An owner supplies where a region's image lies (and, above, its ordering); a family its grid test, its
+// placement of a slot, its blob, its launch and what it says when the blob could not be made.
 RegionSource compeg_decoder::region_source(const compeg_region &region) const
 {
     return RegionSource{out.ptr, uint32_t(out_pitch), region.src, region.dst}; // (image 0, the only one)
@@ -2561,6 +2561,32 @@ struct OrientFamily {
     }
 };
 
+// Luma tensor output: the oriented family's grid, placements and blob (make_orient_blob, unchanged) to the luma kernels'
+// launch; pad is one value.
+struct LumaFamily {
+    using Source = OrientSource;
+    static constexpr const char *kNoBlob = FilterFamily::kNoBlob;
+    OrientFamily orient;
+    const compeg_luma_spec &luma;
+    LumaFamily(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_luma_spec &luma,
+               const compeg_oriented_region *regions, size_t count, const float *pad, void *dst)
+        : orient(spec, filter, nullptr, regions, count, pad, dst), luma(luma)
+    {
+    }
+    bool grid_fits(uint32_t slots) const { return orient.grid_fits(slots); }
+    template <class Owner>
+    Source source(const Owner &owner, size_t r) const { return orient.source(owner, r); }
+    bool make_blob(std::vector<uint32_t> &blob, size_t &tables_at, const Source *sources, uint32_t slots) const
+    {
+        return orient.make_blob(blob, tables_at, sources, slots);
+    }
+    hipError_t launch(const void *records, size_t tables_at, uint32_t slots, hipStream_t stream) const
+    {
+        return launch_luma_tensor(records, tables_at, slots, orient.spec, orient.filter, luma, orient.upright, orient.transposed, orient.pad,
+                                  orient.dst, stream);
+    }
+};
+
 } // namespace
 
 Status compeg_decoder::pack_tensor_regions(const compeg_tensor_spec &spec, const compeg_resize_spec &resize, const compeg_region *regions,
@@ -2597,4 +2623,16 @@ Status compeg_batch::pack_tensor_oriented(const compeg_tensor_spec &spec, const 
                                           const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream)
 {
     return pack_slots(*this, OrientFamily(spec, filter, nhwc, regions, count, pad, dst), count, stream);
+}
+
+Status compeg_decoder::pack_tensor_luma(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_luma_spec &luma,
+                                        const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream)
+{
+    return pack_slots(*this, LumaFamily(spec, filter, luma, regions, count, pad, dst), count, stream);
+}
+
+Status compeg_batch::pack_tensor_luma(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_luma_spec &luma,
+                                      const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream)
+{
+    return pack_slots(*this, LumaFamily(spec, filter, luma, regions, count, pad, dst), count, stream);
 }

@@ -175,6 +175,10 @@ struct compeg_decoder {
     // [count][oh][ow][C], nhwc checked by the caller
     compeg::Status pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
                                         const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
+    // Luma tensor output: pack_tensor_oriented's regions into [count][oh][ow], one channel a slot; luma checked by the
+    // caller, pad one value
+    compeg::Status pack_tensor_luma(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_luma_spec &luma,
+                                    const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
     compeg::Status check_scan_result(bool &fell_back);
     compeg::Status preprocess_on_device(const compeg::ImageData &img, hipStream_t stream, uint32_t &nwords,
                                         uint32_t &nstarts, uint32_t &span, bool &fell_back, size_t blob_bytes,
@@ -294,5 +298,9 @@ struct compeg_batch {
     // [count][oh][ow][C], nhwc checked by the caller
     compeg::Status pack_tensor_oriented(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_nhwc_spec *nhwc,
                                         const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
+    // Luma tensor output: pack_tensor_oriented's regions into [count][oh][ow], one channel a slot; luma checked by the
+    // caller, pad one value
+    compeg::Status pack_tensor_luma(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_luma_spec &luma,
+                                    const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
     std::vector<uint32_t> orientations; // the EXIF orientation tag of every image of the last upload (note_batch_properties)
 };

@@ -658,6 +658,54 @@ int compeg_batch_pack_tensor_nhwc(compeg_batch *batch, const compeg_tensor_spec 
                                   const compeg_nhwc_spec *nhwc, const compeg_oriented_region *regions, size_t count,
                                   const float *pad, void *device_dst, size_t dst_bytes, void *hip_stream);
 
+/* ---- Luma tensor output (extension) ------------------------------------------
+ * compeg_*_pack_tensor_oriented with one channel a slot: what a model whose first convolution takes [N, 1, H, W] reads
+ * of a grayscale camera's frames, and the luma of a colour frame for OCR, optical flow or focus and exposure metrics --
+ * without three identical planes and a slice.  New entry points beside the old ones: no existing call does anything
+ * different.
+ *
+ * Contract (exact).  The source-pixel value: for a pixel (R, G, B, A) of the object's last decode,
+ *   L = (wR * R + wG * G + wB * B + 32768) >> 16
+ * in unsigned 32-bit arithmetic, (wR, wG, wB) = luma's weights, each 0..65536, their sum exactly 65536: L <= 255.  A
+ * decoded grayscale frame has R = G = B = Y, so L = Y exactly, whatever the weights.  With the BT.601 weights L is PIL's
+ * Image.convert("L"), byte for byte.  Presets:
+ *   BT.601  {19595, 38470,  7471}   PIL's Image.convert("L")
+ *   BT.709  {13933, 46871,  4732}
+ *   R, G or B alone: {65536, 0, 0}, {0, 65536, 0}, {0, 0, 65536}
+ * The tensor: destination [count][1][oh][ow], tight -- the same memory as [count][oh][ow] and [count][oh][ow][1] --
+ * (ow, oh) = filter's out_width x out_height: the upright slot.  Element (s, 0, y, x) is, bit for bit, element
+ * (s, 0, y, x) of what compeg_*_pack_tensor_oriented would store with order = RGB, the same dtype, downscale, scale[0],
+ * bias[0], filter, regions and pad {p, p, p}, if every source pixel's R were replaced by its L.  So the prefilter is
+ * P[j][i] = float(sum of L over the k x k block) * (1 / k^2): L is taken per pixel, before the block mean, as
+ * convert("L") followed by a reduce is.  Axis tables, tap order, separately rounded f32 operations,
+ * v = (m * scale[0]) + bias[0], the conversions, the u8 clamp, the orientation table and the tap limits are the oriented
+ * pack's.  Every element of the tensor is written exactly once and no byte outside it is written.
+ * bytes_per_slot = oh * ow * element size; device_dst needs the element type's alignment only.
+ * Of spec, dtype, downscale, reserved, scale[0] and bias[0] are read; order, scale[1..2] and bias[1..2] are validated as
+ * ever and have no effect.  pad points at ONE float on the 0..255 scale (NULL: 0); pad elements are
+ * (pad * scale[0]) + bias[0]. */
+typedef struct compeg_luma_spec {
+    uint32_t weights[3]; /* for R, G, B: each 0..65536, their sum exactly 65536 */
+    uint32_t reserved;   /* 0 */
+} compeg_luma_spec;      /* 16 bytes */
+/* No device needed: compeg_oriented_tensor_shape for the luma calls.  COMPEG_E_INVALID_ARG for what that one rejects, in
+ * its words, and for: luma NULL, a weight above 65536 (the message names the weight), a sum other than 65536 (the
+ * message names the sum), a nonzero reserved word. */
+int compeg_luma_tensor_shape(const compeg_tensor_spec *spec, const compeg_filter_spec *filter, const compeg_luma_spec *luma,
+                             uint32_t width, uint32_t height, const compeg_oriented_region *region, uint32_t *pre_width,
+                             uint32_t *pre_height, size_t *bytes_per_slot);
+/* Like compeg_*_pack_tensor_oriented in everything they say about hip_stream, ordering, timing events, the decoder's
+ * texture, compeg_batch_wait, the copies made before the call returns, the messages and the rejections, with
+ * compeg_luma_tensor_shape's in place of compeg_oriented_tensor_shape's; luma is checked with the specs, before the
+ * object is looked at.  A pad that is not finite is rejected.  dst_bytes below count * bytes_per_slot: the message names
+ * both numbers. */
+int compeg_decoder_pack_tensor_luma(compeg_decoder *dec, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
+                                    const compeg_luma_spec *luma, const compeg_oriented_region *regions, size_t count,
+                                    const float *pad, void *device_dst, size_t dst_bytes, void *hip_stream);
+int compeg_batch_pack_tensor_luma(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
+                                  const compeg_luma_spec *luma, const compeg_oriented_region *regions, size_t count,
+                                  const float *pad, void *device_dst, size_t dst_bytes, void *hip_stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -95,6 +95,15 @@ pub struct compeg_nhwc_spec {
     pub reserved: [u32; 2],
 }
 
+/// The weights of `compeg_*_pack_tensor_luma` (compeg_hip.h, "Luma tensor output"): for R, G and B in 1/65536, their sum
+/// exactly 65536.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct compeg_luma_spec {
+    pub weights: [u32; 3],
+    pub reserved: u32,
+}
+
 pub const COMPEG_OK: c_int = 0;
 pub const COMPEG_E_INVALID_ARG: c_int = -1;
 pub const COMPEG_E_UNSUPPORTED: c_int = -2;
@@ -299,6 +308,19 @@ extern "C" {
                                            hip_stream: *mut c_void) -> c_int;
     pub fn compeg_batch_pack_tensor_nhwc(batch: *mut compeg_batch, spec: *const compeg_tensor_spec, filter: *const compeg_filter_spec,
                                          nhwc: *const compeg_nhwc_spec, regions: *const compeg_oriented_region, count: usize,
+                                         pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
+                                         hip_stream: *mut c_void) -> c_int;
+
+    // Luma tensor output (extension)
+    pub fn compeg_luma_tensor_shape(spec: *const compeg_tensor_spec, filter: *const compeg_filter_spec, luma: *const compeg_luma_spec,
+                                    width: u32, height: u32, region: *const compeg_oriented_region, pre_width: *mut u32,
+                                    pre_height: *mut u32, bytes_per_slot: *mut usize) -> c_int;
+    pub fn compeg_decoder_pack_tensor_luma(dec: *mut compeg_decoder, spec: *const compeg_tensor_spec, filter: *const compeg_filter_spec,
+                                           luma: *const compeg_luma_spec, regions: *const compeg_oriented_region, count: usize,
+                                           pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
+                                           hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_batch_pack_tensor_luma(batch: *mut compeg_batch, spec: *const compeg_tensor_spec, filter: *const compeg_filter_spec,
+                                         luma: *const compeg_luma_spec, regions: *const compeg_oriented_region, count: usize,
                                          pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
                                          hip_stream: *mut c_void) -> c_int;
 }

@@ -337,6 +337,46 @@ impl NhwcSpec {
     }
 }
 
+/// The weights of `Decoder::pack_tensor_luma` / `Batch::pack_tensor_luma` (compeg_hip.h, "Luma tensor output"): per source
+/// pixel `L = (wR R + wG G + wB B + 32768) >> 16`; the destination is `[count][1][oh][ow]`.  A grayscale frame gives its
+/// own values under any of them.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum LumaSpec {
+    /// {19595, 38470, 7471}: PIL's `Image.convert("L")`, byte for byte.
+    Bt601,
+    /// {13933, 46871, 4732}.
+    Bt709,
+    /// R, G or B alone.
+    Red,
+    Green,
+    Blue,
+    /// For R, G and B: each 0..=65536, their sum exactly 65536 (the library checks).
+    Weights([u32; 3]),
+}
+
+impl LumaSpec {
+    fn raw(&self) -> ffi::compeg_luma_spec {
+        let weights = match *self {
+            LumaSpec::Bt601 => [19595, 38470, 7471],
+            LumaSpec::Bt709 => [13933, 46871, 4732],
+            LumaSpec::Red => [65536, 0, 0],
+            LumaSpec::Green => [0, 65536, 0],
+            LumaSpec::Blue => [0, 0, 65536],
+            LumaSpec::Weights(w) => w,
+        };
+        ffi::compeg_luma_spec { weights, reserved: 0 }
+    }
+
+    /// `(pre_width, pre_height, bytes)`: `OrientedRegion::shape` for the luma calls, a third of its bytes.  No device needed.
+    pub fn shape(&self, tensor: &TensorSpec, filter: &FilterSpec, width: u32, height: u32, region: &OrientedRegion) -> Result<(u32, u32, usize)> {
+        let (mut w, mut h, mut n) = (0, 0, 0);
+        check(unsafe {
+            ffi::compeg_luma_tensor_shape(&tensor.raw(), &filter.raw(), &self.raw(), width, height, &region.raw(), &mut w, &mut h, &mut n)
+        })?;
+        Ok((w, h, n))
+    }
+}
+
 /// Device + stream + loaded gfx950 code object.  Immutable after creation and
 /// reference-counted inside the library; share it as `Arc<Gpu>` like the reference.
 pub struct Gpu {
@@ -653,6 +693,19 @@ impl Decoder {
                                                    device_dst, dst_bytes, stream.0))
     }
 
+    /// Extension: `pack_tensor_oriented` with one channel a slot, `[count][1][oh][ow]`; `pad` is one value; of `spec`'s
+    /// scale and bias element 0 is read.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn pack_tensor_luma(&mut self, spec: &TensorSpec, filter: &FilterSpec, luma: &LumaSpec, regions: &[OrientedRegion],
+                                   pad: Option<f32>, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        let raw: Vec<ffi::compeg_oriented_region> = regions.iter().map(OrientedRegion::raw).collect();
+        let pad = pad.as_ref().map_or(ptr::null(), |p| p as *const f32);
+        check(ffi::compeg_decoder_pack_tensor_luma(self.raw.as_ptr(), &spec.raw(), &filter.raw(), &luma.raw(), raw.as_ptr(), raw.len(), pad,
+                                                   device_dst, dst_bytes, stream.0))
+    }
+
     /// Test helper (the reference's tests copy the texture to a buffer): waits and
     /// returns the image's `width x height` corner, tightly packed.
     pub fn read_output(&mut self, width: u32, height: u32) -> Result<Vec<u8>> {
@@ -878,6 +931,19 @@ impl Batch {
         let raw: Vec<ffi::compeg_oriented_region> = regions.iter().map(OrientedRegion::raw).collect();
         let pad = pad.map_or(ptr::null(), |p| p.as_ptr());
         check(ffi::compeg_batch_pack_tensor_nhwc(self.raw.as_ptr(), &spec.raw(), &filter.raw(), &nhwc.raw(), raw.as_ptr(), raw.len(), pad,
+                                                 device_dst, dst_bytes, stream.0))
+    }
+
+    /// Records on `stream` the luma pack of the last decode: `pack_tensor_oriented` with one channel a slot,
+    /// `[count][1][oh][ow]`.  `wait` covers it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn pack_tensor_luma(&mut self, spec: &TensorSpec, filter: &FilterSpec, luma: &LumaSpec, regions: &[OrientedRegion],
+                                   pad: Option<f32>, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        let raw: Vec<ffi::compeg_oriented_region> = regions.iter().map(OrientedRegion::raw).collect();
+        let pad = pad.as_ref().map_or(ptr::null(), |p| p as *const f32);
+        check(ffi::compeg_batch_pack_tensor_luma(self.raw.as_ptr(), &spec.raw(), &filter.raw(), &luma.raw(), raw.as_ptr(), raw.len(), pad,
                                                  device_dst, dst_bytes, stream.0))
     }
 

@@ -37,6 +37,11 @@ The channels-last arm (--nhwc; default table profiles/tensor_nhwc.txt), the same
 with 4 channels beside the planar Batch.pack_tensor_oriented and the chain a user writes without it -- the planar pack into
 a temporary, then .contiguous(memory_format=torch.channels_last) --, to 224x224 and, where the stores are not small beside
 the loads, 1080p -> 1920x1080 without a resize.
+
+The luma arm (--luma; default table profiles/tensor_luma.txt), the same method: Batch.pack_tensor_luma (BT.601) beside the
+three-plane Batch.pack_tensor_oriented of the same launch and the chain a user writes without it -- the oriented pack into a
+temporary, then tmp[:, :1].contiguous() --, to 224x224 from 1080p (orientations 1 and 6) and from 4K, and 1080p ->
+1920x1080 without a resize on colour 4:2:2 frames and on grayscale frames (PIL's L files, restart_marker_blocks = 8).
 """
 import argparse
 import os
@@ -472,6 +477,82 @@ def nhwc_arm(args, torch, compeg_amd, images_of, resident, gpu, stream):
     return "\n".join(lines) + "\n"
 
 
+# the luma arm: (name, (width, height), output size, kernel, element type, orientation, grayscale frames)
+LUMA_CONFIGS = (("1080p -> 224x224 bicubic f16 o=1", (1920, 1080), (224, 224), "bicubic", "f16", 1, False),
+                ("1080p -> 224x224 bicubic f16 o=6", (1920, 1080), (224, 224), "bicubic", "f16", 6, False),
+                ("4K -> 224x224 bicubic f16 o=1", (3840, 2160), (224, 224), "bicubic", "f16", 1, False),
+                ("1080p -> 1920x1080 triangle u8 o=1, colour 4:2:2", (1920, 1080), (1920, 1080), "triangle", "u8", 1, False),
+                ("1080p -> 1920x1080 triangle u8 o=1, grayscale", (1920, 1080), (1920, 1080), "triangle", "u8", 1, True))
+
+
+def luma_arm(args, torch, compeg_amd, images_of, resident, gpu, stream):
+    """The table of the luma arm, as text."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import numpy as np
+
+    import luma_reference as lr   # the header's contract in numpy
+    from tools import gray_probe
+    n, handle = args.batch, stream.cuda_stream
+    torch_type = {"u8": torch.uint8, "f16": torch.float16, "f32": torch.float32}
+    lines = [f"luma tensor output: {n} resident frames per configuration (4:2:2 DRI=4, or grayscale), decoded once; {gpu.name()}; library "
+             f"{os.path.relpath(compeg_amd.LIB_PATH, ROOT)}",
+             "luma = Batch.pack_tensor_luma (BT.601) of whole frames into [N, 1, oh, ow]; planes = Batch.pack_tensor_oriented of the same regions into "
+             "[N, 3, oh, ow]; chain = the oriented pack into a temporary, then tmp[:, :1].contiguous()",
+             f"HIP events on one stream, the arms of a configuration launch by launch in turn, their order turning round from one repetition to the "
+             f"next, one untimed round in front; median of {args.reps} (min .. max), ms"]
+    verdicts = []
+    keys = ["luma", "planes", "chain"]
+    for name, (w, h), (ow, oh), kernel, dtype, o, gray in LUMA_CONFIGS:
+        if gray:
+            count = min(args.distinct, n, 8)
+            files = [gray_probe.encode(gray_probe.picture(w, h, seed), 8, False) for seed in range(count)]
+            items = [compeg_amd.ImageData(j, allow_grayscale=True) for j in files]
+        else:
+            items = images_of(w, h)
+        batch = resident([items[i % len(items)] for i in range(n)])
+        whole = [(i, None, None) for i in range(n)]
+        scale, bias = (1.0, 0.0) if dtype == "u8" else (1.0 / (255.0 * STD[0]), -MEAN[0] / STD[0])
+        kw = dict(orientation=o, kernel=kernel, dtype=dtype, hip_stream=handle)
+        out = {"luma": torch.empty((n, 1, oh, ow), dtype=torch_type[dtype], device="cuda")}
+        out.update({key: torch.empty((n, 3, oh, ow), dtype=torch_type[dtype], device="cuda") for key in ("planes", "tmp")})
+
+        def primer():
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < PRIME_SECONDS:
+                batch.decode(handle)
+                batch.wait()
+
+        def chain():
+            batch.pack_tensor_oriented(out["tmp"], (ow, oh), whole, scale=[scale] * 3, bias=[bias] * 3, **kw)
+            out["chain"] = out["tmp"][:, :1].contiguous()
+
+        arms = [lambda: batch.pack_tensor_luma(out["luma"], (ow, oh), whole, weights="bt601", scale=scale, bias=bias, **kw),
+                lambda: batch.pack_tensor_oriented(out["planes"], (ow, oh), whole, scale=[scale] * 3, bias=[bias] * 3, **kw), chain]
+        t = dict(zip(keys, _timed_in_turn(torch, stream, args.reps, primer, arms)))
+        rgba = batch.read_output(0)
+        want = lr.expected(rgba, (ow, oh), 1, dtype, scale, bias, "bt601", kernel, o=o)
+        planes = lr.orf.expected(rgba, (ow, oh), 1, dtype, [scale] * 3, [bias] * 3, "rgb", kernel, o=o)
+        wrong = {"luma": int((want != out["luma"][0, 0].cpu().numpy()).sum()), "planes": int((planes != out["planes"][0].cpu().numpy()).sum()),
+                 "chain": int((planes[:1] != out["chain"][0].cpu().numpy()).sum())}
+        lines += ["", name]
+        for key in keys:
+            lines.append(f"  {key:<8} {_cell(t[key])}   slot 0: {wrong[key]} elements off the contract")
+        if gray:
+            lines.append(f"  grayscale frames: luma equal to plane 0 of planes in every slot: {bool(torch.equal(out['luma'][:, 0], out['planes'][:, 0]))};"
+                         f" R = G = B in slot 0: {bool(np.array_equal(rgba[..., 0], rgba[..., 1]) and np.array_equal(rgba[..., 0], rgba[..., 2]))}")
+        for other in ("planes", "chain"):
+            a, b = t["luma"], t[other]
+            ratio = statistics.median(a) / statistics.median(b)
+            verdict = ("faster" if statistics.median(a) < statistics.median(b) else "slower") if _gap(a, b) else "within the rows' own spread"
+            lines.append(f"  luma against {other}: {ratio:.2f}, {verdict}")
+            verdicts.append(f"{name}: luma/{other} {ratio:.2f} ({verdict})")
+        print("\n".join(lines[-(len(keys) + 4 + gray):]), file=sys.stderr, flush=True)   # (progress: the table itself is printed at the end)
+        del out, batch
+        torch.cuda.empty_cache()
+    lines += [""] + verdicts
+    return "\n".join(lines) + "\n"
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=256)
@@ -484,9 +565,10 @@ def main():
     p.add_argument("--filtered", action="store_true", help="the filtered arm (Batch.pack_tensor_filtered) instead; default table profiles/tensor_filtered.txt")
     p.add_argument("--oriented", action="store_true", help="the oriented arm (Batch.pack_tensor_oriented) instead; default table profiles/tensor_oriented.txt")
     p.add_argument("--nhwc", action="store_true", help="the channels-last arm (Batch.pack_tensor_nhwc) instead; default table profiles/tensor_nhwc.txt")
+    p.add_argument("--luma", action="store_true", help="the luma arm (Batch.pack_tensor_luma) instead; default table profiles/tensor_luma.txt")
     args = p.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "tensor_nhwc.txt" if args.nhwc else "tensor_oriented.txt" if args.oriented else "tensor_filtered.txt" if args.filtered else "tensor_regions.txt" if args.regions else
+        args.out = os.path.join(ROOT, "profiles", "tensor_luma.txt" if args.luma else "tensor_nhwc.txt" if args.nhwc else "tensor_oriented.txt" if args.oriented else "tensor_filtered.txt" if args.filtered else "tensor_regions.txt" if args.regions else
                                 "tensor_resize_antialias.txt" if args.antialias else "tensor_resize.txt")
 
     import torch
@@ -519,8 +601,9 @@ def main():
         batch.wait()
         return batch
 
-    if args.antialias or args.regions or args.filtered or args.oriented or args.nhwc:
-        text = (nhwc_arm(args, torch, compeg_amd, images_of, resident, gpu, stream) if args.nhwc else
+    if args.antialias or args.regions or args.filtered or args.oriented or args.nhwc or args.luma:
+        text = (luma_arm(args, torch, compeg_amd, images_of, resident, gpu, stream) if args.luma else
+                nhwc_arm(args, torch, compeg_amd, images_of, resident, gpu, stream) if args.nhwc else
                 oriented_arm(args, torch, compeg_amd, images_of, resident, gpu, stream) if args.oriented else
                 filtered_arm(args, torch, compeg_amd, images_of, resident, gpu, stream) if args.filtered else
                 regions_arm(args, torch, F, compeg_amd, images_of, resident, gpu, stream) if args.regions else
