@@ -18,7 +18,8 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
-                   LIB_PATH, METADATA_BYTES, Error, FilterSpec, LumaSpec, NhwcSpec, OrientedRegion, Rect, Region, ResizeSpec, TensorSpec, check,
+                   LIB_PATH, METADATA_BYTES, Error, FilterSpec, LumaSpec, NhwcSpec, OrientedRegion, PlanesLayout, PlanesSpec, Rect, Region, ResizeSpec,
+                   TensorSpec, check,
                    lib)
 
 __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Texture", "Error", "HostBuffer", "JpegList",
@@ -26,11 +27,11 @@ __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Te
            "resized_tensor_shape", "RESIZE_FILTERS", "ResizeSpec", "Rect", "Region", "FIT_ALIGNS", "region_fit",
            "region_tensor_shape", "FILTER_KERNELS", "FilterSpec", "filtered_tensor_shape", "ORIENTATIONS", "OrientedRegion",
            "orient_rect", "oriented_tensor_shape", "NhwcSpec", "nhwc_tensor_shape", "LumaSpec", "LUMA_WEIGHTS",
-           "luma_tensor_shape"]
+           "luma_tensor_shape", "PlanesSpec", "PlanesLayout", "PLANES_FORMATS", "PLANES_CHROMA", "planes_shape"]
 
 
 # compeg_decoder_last_kernel / compeg_batch_last_kernel (include/compeg_hip.h: COMPEG_KERNEL_*)
-KERNEL_NAMES = ("none", "fused", "pair", "coop_team", "generic", "split", "fused_layout", "fused_stream", "walk_mcu")
+KERNEL_NAMES = ("none", "fused", "pair", "coop_team", "generic", "split", "fused_layout", "fused_stream", "walk_mcu", "planes")
 
 
 def version():
@@ -404,6 +405,41 @@ def _luma_device_range(dst, size, count):
     return address, slots * oh * ow * itemsize
 
 
+# Planar YCbCr output (include/compeg_hip.h: COMPEG_PLANES_*, COMPEG_CHROMA_*): formats and chroma options by name
+PLANES_FORMATS = {"planar": 0, "semiplanar": 1, "yuyv": 2, "uyvy": 3}
+PLANES_CHROMA = {"coded": 0, "420": 1}
+
+
+def _planes_spec(format, chroma, pitch):
+    """compeg_planes_spec from names (or the header's numbers, which the library checks); pitch: None (tight), one
+    number (the luma pitch) or (luma_pitch, chroma_pitch), 0 = tight."""
+    if isinstance(format, str) and format not in PLANES_FORMATS:
+        raise Error(f"unknown planes format {format!r} (one of {', '.join(PLANES_FORMATS)})")
+    if isinstance(chroma, str) and chroma not in PLANES_CHROMA:
+        raise Error(f"unknown planes chroma option {chroma!r} (one of {', '.join(PLANES_CHROMA)})")
+    spec = PlanesSpec()
+    spec.format = PLANES_FORMATS[format] if isinstance(format, str) else format
+    spec.chroma = PLANES_CHROMA[chroma] if isinstance(chroma, str) else chroma
+    if pitch is None:
+        pitch = (0, 0)
+    elif not isinstance(pitch, (tuple, list)):
+        pitch = (pitch, 0)
+    spec.luma_pitch, spec.chroma_pitch = int(pitch[0]), int(pitch[1])
+    return spec
+
+
+def planes_shape(width, height, sampling=(2, 1), components=3, format="planar", chroma="coded", pitch=None):
+    """(planes, total_bytes) of one width x height image whose luma is sampled `sampling` (ImageData.sampling()) --
+    compeg_planes_shape; no device needed.  planes: a tuple of dicts offset / pitch / row_bytes / width / height, one per
+    plane, in the order they lie; the caller makes its views of a u8 destination from them."""
+    spec = _planes_spec(format, chroma, pitch)
+    lay = PlanesLayout()
+    check(lib.compeg_planes_shape(C.byref(spec), width, height, components, sampling[0], sampling[1], C.byref(lay)))
+    planes = tuple({"offset": lay.offset[p], "pitch": lay.pitch[p], "row_bytes": lay.row_bytes[p], "width": lay.width[p],
+                    "height": lay.height[p]} for p in range(lay.planes))
+    return planes, lay.total_bytes
+
+
 def _host_view(data):
     a = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
     return np.ascontiguousarray(a)
@@ -542,6 +578,13 @@ class ImageData:
         """Extension (compeg_image_components): 3, or 1 for a grayscale image (allow_grayscale)."""
         return lib.compeg_image_components(self._h)
 
+    def sampling(self):
+        """Extension (compeg_image_sampling): the luma component's sampling factors (h, v) -- (2, 1) for 4:2:2, (1, 1)
+        for 4:4:4 and grayscale, (1, 2) for 4:4:0, (2, 2) for 4:2:0."""
+        hs, vs = C.c_uint32(), C.c_uint32()
+        check(lib.compeg_image_sampling(self._h, C.byref(hs), C.byref(vs)))
+        return hs.value, vs.value
+
     @property
     def orientation(self):
         """Extension (compeg_image_orientation): the file's EXIF orientation tag, 1..8; 1 where it has no usable one."""
@@ -673,6 +716,21 @@ class Decoder:
         op = C.c_void_p()
         check(lib.compeg_decoder_decode_blocking(self._h, data._h, C.byref(op)))
         return DecodeOp(op, self)
+
+    def decode_planes(self, data, dst, format="planar", chroma="coded", pitch=None, hip_stream=0, blocking=False):
+        """Extension (compeg_decoder_decode_planes): uploads and preprocesses `data` as enqueue does and records, on hip_stream
+        (0 = the gpu's stream), a decode that writes the file's own Y, Cb and Cr samples into caller-owned device memory as
+        planes_shape lays them out -- no colour step, no upsampling.  dst: (address, nbytes), a tensor, or a
+        __cuda_array_interface__ object of at least total_bytes.  The texture and what the packs read are not touched.
+        Returns without waiting; blocking=True (the gpu's stream only) waits for the decode."""
+        spec = _planes_spec(format, chroma, pitch)
+        addr, nbytes = _device_range(dst)
+        if blocking:
+            if hip_stream:
+                raise Error("decode_planes: blocking=True records on the gpu's own stream")
+            check(lib.compeg_decoder_decode_planes_blocking(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes))
+        else:
+            check(lib.compeg_decoder_decode_planes(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
 
     def last_warning(self):
         return lib.compeg_decoder_last_warning(self._h).decode()
@@ -863,6 +921,15 @@ class Batch:
 
     def decode(self, hip_stream=0):
         check(lib.compeg_batch_decode(self._h, C.c_void_p(hip_stream)))
+
+    def decode_planes(self, dst, format="planar", chroma="coded", pitch=None, hip_stream=0):
+        """Extension (compeg_batch_decode_planes): records, on hip_stream (0 = the gpu's stream), a decode of the last upload's
+        images (all of one size and sampling) that writes each one's own Y, Cb and Cr samples into caller-owned device memory,
+        image i at i * total_bytes of planes_shape -- no colour step, no upsampling.  dst: (address, nbytes), a tensor, or a
+        __cuda_array_interface__ object.  The RGBA outputs are not touched.  Returns without waiting; wait() covers it."""
+        spec = _planes_spec(format, chroma, pitch)
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_batch_decode_planes(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
 
     def wait(self):
         check(lib.compeg_batch_wait(self._h))

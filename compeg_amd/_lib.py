@@ -66,6 +66,18 @@ class LumaSpec(C.Structure):
     _fields_ = [("weights", C.c_uint32 * 3), ("reserved", C.c_uint32)]
 
 
+class PlanesSpec(C.Structure):
+    """compeg_planes_spec (include/compeg_hip.h, "Planar YCbCr output"): format, chroma option and the two pitches."""
+    _fields_ = [("format", C.c_uint32), ("chroma", C.c_uint32), ("luma_pitch", C.c_uint32), ("chroma_pitch", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class PlanesLayout(C.Structure):
+    """compeg_planes_layout: where one image's planes lie and how large they are."""
+    _fields_ = [("planes", C.c_uint32), ("reserved", C.c_uint32), ("total_bytes", C.c_uint64), ("offset", C.c_uint64 * 3),
+                ("pitch", C.c_uint32 * 3), ("row_bytes", C.c_uint32 * 3), ("width", C.c_uint32 * 3), ("height", C.c_uint32 * 3)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -90,6 +102,7 @@ def _load():
         "compeg_image_height": (u32, [vp]),
         "compeg_image_parallelism": (u32, [vp]),
         "compeg_image_components": (u32, [vp]),
+        "compeg_image_sampling": (i, [vp, pu32, pu32]),
         "compeg_image_metadata": (vp, [vp]),
         "compeg_image_huffman_l1": (vp, [vp]),
         "compeg_image_huffman_l2": (vp, [vp, psz]),
@@ -168,6 +181,10 @@ def _load():
         "compeg_luma_tensor_shape": (i, [C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(LumaSpec), u32, u32, C.POINTER(OrientedRegion), pu32, pu32, psz]),
         "compeg_decoder_pack_tensor_luma": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(LumaSpec), C.POINTER(OrientedRegion), sz, C.POINTER(C.c_float), vp, sz, vp]),
         "compeg_batch_pack_tensor_luma": (i, [vp, C.POINTER(TensorSpec), C.POINTER(FilterSpec), C.POINTER(LumaSpec), C.POINTER(OrientedRegion), sz, C.POINTER(C.c_float), vp, sz, vp]),
+        "compeg_planes_shape": (i, [C.POINTER(PlanesSpec), u32, u32, u32, u32, u32, C.POINTER(PlanesLayout)]),
+        "compeg_batch_decode_planes": (i, [vp, C.POINTER(PlanesSpec), vp, sz, vp]),
+        "compeg_decoder_decode_planes": (i, [vp, vp, C.POINTER(PlanesSpec), vp, sz, vp]),
+        "compeg_decoder_decode_planes_blocking": (i, [vp, vp, C.POINTER(PlanesSpec), vp, sz]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("COMPEG_LIB") and not hasattr(L, name):

@@ -1788,3 +1788,211 @@ int compeg_batch_pack_tensor_luma(compeg_batch *batch, const compeg_tensor_spec 
 }
 
 } // extern "C"
+
+/* ---- Planar YCbCr output ---------------------------------------------------- */
+
+namespace {
+
+const char *sampling_name(uint32_t components, uint32_t hs, uint32_t vs)
+{
+    if (components == 1)
+        return "grayscale";
+    return hs == 2 && vs == 1 ? "4:2:2" : hs == 1 && vs == 1 ? "4:4:4" : hs == 1 && vs == 2 ? "4:4:0" : hs == 2 && vs == 2 ? "4:2:0" : "unknown";
+}
+
+// compeg_planes_spec as the header has it, laid out for a width x height image: 0 with *out filled in, or the error
+// recorded.  (The texts name values, not the header's macros.)
+int planes_layout(const compeg_planes_spec *spec, uint32_t width, uint32_t height, uint32_t components, uint32_t hs, uint32_t vs,
+                  compeg_planes_layout *out)
+{
+    if (!spec)
+        return fail(COMPEG_E_INVALID_ARG, "spec is NULL");
+    if (!out)
+        return fail(COMPEG_E_INVALID_ARG, "layout is NULL");
+    if (spec->format > COMPEG_PLANES_UYVY)
+        return fail(COMPEG_E_INVALID_ARG, ("planes spec: format " + std::to_string(spec->format) + " is none of 0 (planar), 1 (semiplanar), 2 (yuyv), 3 (uyvy)").c_str());
+    if (spec->chroma > COMPEG_CHROMA_420)
+        return fail(COMPEG_E_INVALID_ARG, ("planes spec: chroma " + std::to_string(spec->chroma) + " is neither 0 (as coded) nor 1 (4:2:0)").c_str());
+    for (int i = 0; i < 4; i++)
+        if (spec->reserved[i] != 0u)
+            return fail(COMPEG_E_INVALID_ARG, "planes spec: reserved must be 0");
+    const bool gray = components == 1;
+    if (components != 1 && components != 3)
+        return fail(COMPEG_E_INVALID_ARG, ("planes: " + std::to_string(components) + " components, an image has 1 or 3").c_str());
+    if (gray ? !(hs == 1 && vs == 1) : !((hs == 1 || hs == 2) && (vs == 1 || vs == 2)))
+        return fail(COMPEG_E_INVALID_ARG, ("planes: luma sampling " + std::to_string(hs) + "x" + std::to_string(vs) +
+                                           " is none of 2x1, 1x1, 1x2, 2x2 (1x1 for a grayscale image)").c_str());
+    if (width == 0 || height == 0)
+        return fail(COMPEG_E_INVALID_ARG, "planes: the image has no pixels");
+    const bool packed = spec->format >= COMPEG_PLANES_YUYV, is422 = !gray && hs == 2 && vs == 1;
+    const bool half = spec->chroma == COMPEG_CHROMA_420;
+    if (half && packed)
+        return fail(COMPEG_E_INVALID_ARG, "planes spec: chroma 1 (4:2:0) goes with the planar and semiplanar formats only, not with a packed one");
+    if (packed && !is422)
+        return fail(COMPEG_E_UNSUPPORTED, (std::string("planes: the packed formats yuyv and uyvy take 4:2:2 files only, this one is ") +
+                                           sampling_name(components, hs, vs)).c_str());
+    if (half && !is422)
+        return fail(COMPEG_E_UNSUPPORTED, (std::string("planes: chroma 1 (4:2:0) is made from 4:2:2 files only, this one is ") +
+                                           sampling_name(components, hs, vs)).c_str());
+    compeg_planes_layout l;
+    memset(&l, 0, sizeof l);
+    const uint32_t cw = (width + hs - 1) / hs, ch = half ? (height + 1) / 2 : (height + vs - 1) / vs;
+    if (packed) {
+        l.planes = 1;
+        l.width[0] = width;
+        l.height[0] = height;
+        l.row_bytes[0] = 4u * ((width + 1) / 2);
+    } else {
+        l.planes = gray ? 1u : (spec->format == COMPEG_PLANES_SEMIPLANAR ? 2u : 3u);
+        l.width[0] = width;
+        l.height[0] = height;
+        l.row_bytes[0] = width;
+        for (uint32_t p = 1; p < l.planes; p++) {
+            l.width[p] = cw;
+            l.height[p] = ch;
+            l.row_bytes[p] = l.planes == 2 ? 2u * cw : cw;
+        }
+    }
+    uint64_t at = 0;
+    for (uint32_t p = 0; p < l.planes; p++) {
+        const uint32_t given = p == 0 ? spec->luma_pitch : spec->chroma_pitch;
+        if (given != 0u && given < l.row_bytes[p])
+            return fail(COMPEG_E_INVALID_ARG, (std::string("planes spec: ") + (p == 0 ? "luma_pitch " : "chroma_pitch ") + std::to_string(given) +
+                                               " is below the row's " + std::to_string(l.row_bytes[p]) + " bytes").c_str());
+        l.pitch[p] = given ? given : l.row_bytes[p];
+        l.offset[p] = at;
+        at += uint64_t(l.pitch[p]) * l.height[p];
+    }
+    l.total_bytes = at;
+    *out = l;
+    return COMPEG_OK;
+}
+
+PlanesTarget planes_target(const compeg_planes_spec &spec, const compeg_planes_layout &l, void *device_dst)
+{
+    PlanesTarget t{};
+    t.dst = static_cast<uint8_t *>(device_dst);
+    t.image_stride = l.total_bytes;
+    for (int p = 0; p < 3; p++) {
+        t.offset[p] = l.offset[p];
+        t.pitch[p] = l.pitch[p];
+        t.row_bytes[p] = l.row_bytes[p];
+        t.rows[p] = l.height[p];
+    }
+    t.format = spec.format;
+    t.chroma420 = spec.chroma == COMPEG_CHROMA_420 ? 1u : 0u;
+    return t;
+}
+
+int check_planes_destination(const void *device_dst, size_t dst_bytes, uint64_t total, size_t images)
+{
+    if (!device_dst)
+        return fail(COMPEG_E_INVALID_ARG, "device_dst is NULL");
+    if (uint64_t(dst_bytes) / total < images)
+        return fail(COMPEG_E_INVALID_ARG, ("planes: dst_bytes is " + std::to_string(dst_bytes) + ", " + std::to_string(images) + " image(s) of " +
+                                           std::to_string(total) + " bytes need " + std::to_string(total * images)).c_str());
+    return COMPEG_OK;
+}
+
+int decoder_planes(compeg_decoder *dec, const compeg_image *img, const compeg_planes_spec *spec, void *device_dst, size_t dst_bytes,
+                   hipStream_t stream)
+{
+    const ImageData &data = *img->data;
+    compeg_planes_layout l;
+    int rc = planes_layout(spec, data.width, data.height, data.components, data.metadata.components[0].hsample, data.metadata.components[0].vsample, &l);
+    if (rc == COMPEG_OK)
+        rc = check_planes_destination(device_dst, dst_bytes, l.total_bytes, 1);
+    if (rc != COMPEG_OK)
+        return rc;
+    const PlanesTarget target = planes_target(*spec, l, device_dst);
+    Status s = dec->enqueue(data, stream, nullptr, false, &target);
+    return s.ok() ? ok() : fail(s);
+}
+
+} // namespace
+
+extern "C" {
+
+int compeg_image_sampling(const compeg_image *img, uint32_t *hsample, uint32_t *vsample)
+{
+    if (!img)
+        return fail(COMPEG_E_INVALID_ARG, "img is NULL");
+    if (hsample)
+        *hsample = img->data->metadata.components[0].hsample;
+    if (vsample)
+        *vsample = img->data->metadata.components[0].vsample;
+    return ok();
+}
+
+int compeg_planes_shape(const compeg_planes_spec *spec, uint32_t width, uint32_t height, uint32_t components, uint32_t hsample,
+                        uint32_t vsample, compeg_planes_layout *layout)
+{
+    return guarded([&] {
+        const int rc = planes_layout(spec, width, height, components, hsample, vsample, layout);
+        return rc == COMPEG_OK ? ok() : rc;
+    });
+}
+
+int compeg_batch_decode_planes(compeg_batch *batch, const compeg_planes_spec *spec, void *device_dst, size_t dst_bytes, void *hip_stream)
+{
+    return guarded([&] {
+        if (!batch)
+            return fail(COMPEG_E_INVALID_ARG, null_text(batch));
+        if (!spec)
+            return fail(COMPEG_E_INVALID_ARG, "spec is NULL");
+        Status s = batch->finish_upload(); // (the descriptors looked at below are the finished upload's)
+        if (!s.ok())
+            return fail(s);
+        if (batch->count == 0)
+            return fail(COMPEG_E_INVALID_ARG, "planes: nothing uploaded yet");
+        const ImageDesc &first = batch->descs[0];
+        const uint32_t comps0 = first.dus_per_mcu == 1 ? 1u : 3u;
+        for (size_t i = 1; i < batch->count; i++) {
+            const ImageDesc &d = batch->descs[i];
+            if (d.out_w != first.out_w || d.out_h != first.out_h)
+                return fail(COMPEG_E_INVALID_ARG, ("planes: the batch's images are not all of one size (image " + std::to_string(i) + " is " +
+                                                   std::to_string(d.out_w) + "x" + std::to_string(d.out_h) + ", image 0 " + std::to_string(first.out_w) + "x" +
+                                                   std::to_string(first.out_h) + ")").c_str());
+            const uint32_t comps = d.dus_per_mcu == 1 ? 1u : 3u;
+            if (comps != comps0 || d.hsample[0] != first.hsample[0] || d.vsample[0] != first.vsample[0])
+                return fail(COMPEG_E_INVALID_ARG, (std::string("planes: the batch's images are not all of one sampling (image ") + std::to_string(i) + " is " +
+                                                   sampling_name(comps, d.hsample[0], d.vsample[0]) + ", image 0 " +
+                                                   sampling_name(comps0, first.hsample[0], first.vsample[0]) + ")").c_str());
+        }
+        compeg_planes_layout l;
+        int rc = planes_layout(spec, first.out_w, first.out_h, comps0, first.hsample[0], first.vsample[0], &l);
+        if (rc == COMPEG_OK)
+            rc = check_planes_destination(device_dst, dst_bytes, l.total_bytes, batch->count);
+        if (rc != COMPEG_OK)
+            return rc;
+        s = batch->decode_planes(planes_target(*spec, l, device_dst), first.hsample[0], comps0 == 1 ? 0u : first.vsample[0],
+                                 stream_of(*batch, hip_stream));
+        return s.ok() ? ok() : fail(s);
+    });
+}
+
+int compeg_decoder_decode_planes(compeg_decoder *dec, const compeg_image *img, const compeg_planes_spec *spec, void *device_dst,
+                                 size_t dst_bytes, void *hip_stream)
+{
+    return guarded([&] {
+        if (!dec || !img)
+            return fail(COMPEG_E_INVALID_ARG, "NULL argument");
+        return decoder_planes(dec, img, spec, device_dst, dst_bytes, stream_of(*dec, hip_stream));
+    });
+}
+
+int compeg_decoder_decode_planes_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_planes_spec *spec, void *device_dst,
+                                          size_t dst_bytes)
+{
+    return guarded([&] {
+        if (!dec || !img)
+            return fail(COMPEG_E_INVALID_ARG, "NULL argument");
+        const int rc = decoder_planes(dec, img, spec, device_dst, dst_bytes, dec->gpu->stream);
+        if (rc != COMPEG_OK)
+            return rc;
+        const hipError_t e = hipStreamSynchronize(dec->gpu->stream);
+        return e == hipSuccess ? ok() : fail(hip_status(e, "hipStreamSynchronize"));
+    });
+}
+
+} // extern "C"

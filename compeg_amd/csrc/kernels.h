@@ -7,6 +7,7 @@
 
 #include "compeg_hip.h"
 #include "device_types.h"
+#include "planes_types.h"
 #include "region_types.h"
 
 namespace compeg {
@@ -192,6 +193,14 @@ hipError_t launch_nhwc_tensor(const void *device_blob, size_t tables_at, uint32_
 hipError_t launch_luma_tensor(const void *device_blob, size_t tables_at, uint32_t slots, const compeg_tensor_spec &spec,
                               const compeg_filter_spec &filter, const compeg_luma_spec &luma, bool upright, bool transposed, const float *pad,
                               void *dst, hipStream_t stream);
+
+// Planes decode (planes_kernels.hip, planes_body.h): the images' samples, component by component at the component's own
+// resolution, into the caller's memory as `target` lays it out; a lane per restart interval behind whole windows.
+// hs x vs: the luma sampling all images of the launch share (1 x 0: grayscale images); plan: plan_huffman's with
+// wave_cap = planes_wave_cap.  target: validated by the caller.
+uint32_t planes_wave_cap(uint32_t hs, uint32_t vs);
+hipError_t launch_planes(const ImageDesc *descs, uint32_t images, uint32_t max_intervals, const HuffLdsPlan &plan, uint32_t hs, uint32_t vs,
+                         const PlanesTarget &target, hipStream_t stream);
 
 #if defined(CG_AC_STAMPS)
 // diagnostic build: AC-loop cycle counters (kernels_body.h)

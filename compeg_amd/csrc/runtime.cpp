@@ -615,7 +615,7 @@ Status compeg_decoder::finish_deferred(const ImageData &img, hipStream_t stream)
 }
 
 // Counterpart of Decoder::enqueue (src/lib.rs:385-477).
-Status compeg_decoder::enqueue(const ImageData &img, hipStream_t stream, bool *changed, bool may_defer)
+Status compeg_decoder::enqueue(const ImageData &img, hipStream_t stream, bool *changed, bool may_defer, const PlanesTarget *planes)
 {
     EnqueueTrace trace;
     const auto t_enter = std::chrono::steady_clock::now();
@@ -645,8 +645,9 @@ Status compeg_decoder::enqueue(const ImageData &img, hipStream_t stream, bool *c
 
     // DynamicTexture::reserve (dynamic.rs:214-248): recreate at exactly the
     // requested size when either dimension is too small.
+    // (a planes decode writes the caller's memory: the texture stays what the last RGBA decode left)
     bool realloc_out = false;
-    if (img.width > out_w || img.height > out_h || !out.ptr) {
+    if (!planes && (img.width > out_w || img.height > out_h || !out.ptr)) {
         // (rows of whole MCUs, 16 pixels each way: an MCU the extent's edge cuts is stored whole, rows begin on 64-byte
         // boundaries whatever the width -- 256 x 1080x1920 portrait frames 1608 -> 8xx us, device_types.h: out_alloc_h)
         const size_t pitch = align_up(size_t(img.width), 16) * 4;
@@ -847,11 +848,13 @@ Status compeg_decoder::enqueue(const ImageData &img, hipStream_t stream, bool *c
     }
     last_stream = stream;
     last_md = md;
-    last_w = img.width;
-    last_h = img.height;
-    last_orientation = img.orientation;
     last_desc_dev = db;
-    have_last = true;
+    if (!planes) { // (what the texture's readers and the packs go by: the last RGBA decode's)
+        last_w = img.width;
+        last_h = img.height;
+        last_orientation = img.orientation;
+        have_last = true;
+    }
 
     last_kernel = COMPEG_KERNEL_NONE;
     if (total_dus == 0) {
@@ -871,12 +874,17 @@ Status compeg_decoder::enqueue(const ImageData &img, hipStream_t stream, bool *c
     const uint32_t luma_h = md.components[0].hsample, luma_v = layout_vs(img);
     // (8-pixel MCUs in pairs: rows of 64 bytes; of an odd interval the last MCU alone.  Intervals of one MCU: the single form)
     const bool mcu_pairs = luma_h == 1 && md.restart_interval >= 2u;
-    const HuffLdsPlan plan = plan_huffman(md.total_restart_intervals, 1, staged_lut_entries(img), span,
-                                          fused || !is_422(img), is_422(img) ? 0u : fused_layout_wave_cap(luma_h, luma_v, mcu_pairs));
+    const HuffLdsPlan plan = plan_huffman(md.total_restart_intervals, 1, staged_lut_entries(img), span, fused || !is_422(img) || planes,
+                                          planes ? planes_wave_cap(luma_h, luma_v) : is_422(img) ? 0u : fused_layout_wave_cap(luma_h, luma_v, mcu_pairs));
     last_span = span;
     last_plan = plan;
     trace.mark("plan");
-    if (!is_422(img)) {
+    if (planes) {
+        // the planes decode: one kernel per sampling, a lane per restart interval, into the caller's memory
+        CG_HIP(launch_planes(reinterpret_cast<const ImageDesc *>(db), 1, md.total_restart_intervals, plan, luma_h, luma_v, *planes, stream));
+        last_kernel = COMPEG_KERNEL_PLANES;
+        coefficients_valid = false;
+    } else if (!is_422(img)) {
         // extension layouts (4:4:4, 4:4:0, 4:2:0): one fused kernel per layout (the development pipeline keeps the
         // two-kernel route: entropy stage with the IDCT in place, generic composite)
         if (use_fused_pipeline() && layout_has_stream_kernel(luma_h, luma_v, mcu_pairs) &&
@@ -2313,6 +2321,33 @@ Status compeg_batch::decode(hipStream_t stream)
     output_decoded = true;
     last_stream = stream;
     return Status{};
+}
+
+// Planes decode: the images of the last upload into the caller's memory.  It reads what decode() reads and writes
+// nothing of the batch's own but the units' scan results (mode 2), so it orders itself like a pack: behind the batch's
+// previous work on another stream, and the batch's next work on another stream behind it (note_pack: last_stream).
+Status compeg_batch::decode_planes(const PlanesTarget &target, uint32_t hs, uint32_t vs, hipStream_t stream)
+{
+    CG_TRY(finish_upload());
+    if (count == 0)
+        return Status{};
+    CG_HIP(hipSetDevice(gpu->device));
+    CG_TRY(order_pack_behind_decode(stream));
+    const ImageDesc *dd = static_cast<const ImageDesc *>(dev_descs.ptr);
+    const uint32_t n = uint32_t(count);
+    const uint32_t step = chunk ? std::min(chunk, n) : n;
+    if (preprocess_mode == 2 && host_fallbacks == 0)
+        CG_HIP(launch_scan(static_cast<const ScanDesc *>(scan_descs.ptr), n, max_tiles, stream));
+    for (uint32_t at = 0; at < n; at += step) {
+        const uint32_t m = std::min(step, n - at);
+        const HuffLdsPlan plan = plan_huffman(max_intervals, m, max_l2, max_span, true, planes_wave_cap(hs, vs));
+        PlanesTarget part = target;
+        part.dst = target.dst + uint64_t(at) * target.image_stride;
+        CG_HIP(launch_planes(dd + at, m, max_intervals, plan, hs, vs, part, stream));
+    }
+    last_kernel = COMPEG_KERNEL_PLANES;
+    decode_recorded = true; // (something of the batch's is on last_stream: what order_pack_behind_decode asks)
+    return note_pack(stream);
 }
 
 // Tensor output.  Every pack reads `out` on a stream of the caller's choice: behind the last decode (the scheme of

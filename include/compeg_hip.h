@@ -113,6 +113,10 @@ uint32_t compeg_image_height(const compeg_image *img);      /* lib.rs:834-837 */
 uint32_t compeg_image_parallelism(const compeg_image *img); /* lib.rs:838-846 */
 /* Extension: components of the frame -- 3, or 1 for a grayscale image (COMPEG_PARSE_GRAYSCALE). */
 uint32_t compeg_image_components(const compeg_image *img);
+/* Extension: the luma component's sampling factors against chroma -- 2x1 (4:2:2), 1x1 (4:4:4), 1x2 (4:4:0), 2x2
+ * (4:2:0); 1x1 for a grayscale image (compeg_image_components tells it from 4:4:4).  What a caller sizes the planes
+ * of compeg_planes_shape with.  Either output may be NULL. */
+int compeg_image_sampling(const compeg_image *img, uint32_t *hsample, uint32_t *vsample);
 /* What the reference uploads per image (src/lib.rs:397-407), exposed so that a
  * binding's tests can compare them byte for byte: the 1112-byte Metadata
  * block, the 2048-byte L1 LUT, the L2 LUT, and the location of the
@@ -194,6 +198,8 @@ int compeg_decoder_last_stage_times(const compeg_decoder *dec, compeg_stage_time
                                        finds where the MCUs begin, then a lane per MCU decodes (batches of few or long
                                        restart intervals; single images whose intervals the cooperative kernel does not
                                        take or takes less well: beyond 256 MCUs, no DRI at all, a 4K frame's 1080 teams) */
+#define COMPEG_KERNEL_PLANES 9       /* decode_planes_422 / _444 / _440 / _420 / _gray_kernel: a planes decode
+                                       (compeg_*_decode_planes), a lane per restart interval */
 int compeg_decoder_last_kernel(const compeg_decoder *dec);
 /* Extension: on != 0 moves the scan preprocessing of every following decode
  * from the host (the reference's data flow, default) to the device-side scan
@@ -705,6 +711,94 @@ int compeg_decoder_pack_tensor_luma(compeg_decoder *dec, const compeg_tensor_spe
 int compeg_batch_pack_tensor_luma(compeg_batch *batch, const compeg_tensor_spec *spec, const compeg_filter_spec *filter,
                                   const compeg_luma_spec *luma, const compeg_oriented_region *regions, size_t count,
                                   const float *pad, void *device_dst, size_t dst_bytes, void *hip_stream);
+
+/* ---- Planar YCbCr output (extension) -----------------------------------------
+ * A second kind of decode: every component's 8-bit samples as the file codes them, at the component's own resolution,
+ * written into caller-owned device memory -- no colour conversion, no chroma upsampling, no clamp beyond the
+ * transform's own.  What a hardware video encoder (NV12 / NV16 / I420 / YUY2), a display path or a model trained on
+ * YUV or luma reads, without a decode to RGBA and a conversion back.  New entry points beside the old ones: the RGBA
+ * output, compeg_decoder_output / _read_output, and what the tensor packs see as "the last decode" are not touched by
+ * a planes decode, and without these calls nothing behaves differently.
+ *
+ * Values.  The bytes written for a data unit are exactly the 64 samples the decoder holds in front of its colour
+ * step: Y as decoded, Cb and Cr as decoded (0..255, 128 neutral).  The entropy decode and the transform are those of
+ * every other decode (32 retained coefficients, the entropy quirks unless COMPEG_PARSE_STANDARD_ENTROPY, the wrapping
+ * predictor, the f32 transform, truncation toward zero).  MCUs behind the last complete restart interval are not
+ * decoded and their bytes in the destination are NOT WRITTEN: the memory is the caller's, its previous contents stay.
+ *
+ * Geometry.  Component c of a W x H image is ceil(W hs_c / hmax) x ceil(H vs_c / vmax) samples; a grayscale image has
+ * the luma plane only.  Nothing outside these extents is ever written -- not the rest of a row inside its pitch, not
+ * a row below the last; a data unit the extent cuts is stored in part.
+ *
+ * format:
+ *   PLANAR      Y, then Cb, then Cr: I422 / I444 / I440 / I420 / Y800 by the file's sampling
+ *   SEMIPLANAR  Y, then one plane of interleaved Cb Cr pairs: NV16 / NV24 / NV12 (no name for 4:4:0)
+ *   YUYV, UYVY  one plane of Y0 Cb Y1 Cr (Cb Y0 Cr Y1) groups, 4:2:2 files only -- COMPEG_E_UNSUPPORTED otherwise.  A
+ *               row is ceil(W / 2) groups: for an odd W the last group's second luma byte is the sample the file
+ *               encodes to the right of the edge, not a replica.
+ * chroma:
+ *   AS_CODED    the default
+ *   CHROMA_420  4:2:2 files only, PLANAR or SEMIPLANAR (I420 / NV12): chroma row r is (a + b + 1) >> 1 of rows 2 r and
+ *               2 r + 1 of the coded chroma, sample by sample; the chroma planes are ceil(H / 2) rows.  For an odd H the
+ *               last row's partner is the row the file encodes below the edge (MCUs are whole), not a replica.
+ *               COMPEG_E_UNSUPPORTED for any other sampling, COMPEG_E_INVALID_ARG with a packed format.
+ * luma_pitch / chroma_pitch: bytes from row to row of the first plane (Y, or the packed plane) and of the chroma
+ *   planes (Cb and Cr, or CbCr); 0 = tight (the row's bytes), else any value >= the row's bytes.
+ * Plane offsets are the library's: plane p + 1 begins at plane p's offset + pitch * height, the first at 0 -- no
+ *   alignment is added (alignment 1), so tight planes are byte-compatible with what an encoder expects of
+ *   I420 / NV12 / NV16 / YUY2 buffers.  Rows whose plane base and pitch are multiples of 16 bytes (8 for the 8-byte rows
+ *   of Cb / Cr planes and of 4:4:4 / 4:4:0 / grayscale luma) take the vector-store path; any other destination is
+ *   stored byte by byte and is not refused. */
+#define COMPEG_PLANES_PLANAR 0
+#define COMPEG_PLANES_SEMIPLANAR 1
+#define COMPEG_PLANES_YUYV 2
+#define COMPEG_PLANES_UYVY 3
+#define COMPEG_CHROMA_AS_CODED 0
+#define COMPEG_CHROMA_420 1
+typedef struct compeg_planes_spec {
+    uint32_t format, chroma;           /* COMPEG_PLANES_*, COMPEG_CHROMA_* */
+    uint32_t luma_pitch, chroma_pitch; /* bytes; 0 = tight */
+    uint32_t reserved[4];              /* 0 */
+} compeg_planes_spec;                  /* 32 bytes */
+typedef struct compeg_planes_layout {
+    uint32_t planes;       /* 1, 2 or 3 */
+    uint32_t reserved;     /* written as 0 */
+    uint64_t total_bytes;  /* one image's planes, the last plane's last row at its full pitch */
+    uint64_t offset[3];    /* per plane: its first byte ... */
+    uint32_t pitch[3];     /* ... bytes from row to row ... */
+    uint32_t row_bytes[3]; /* ... bytes of a row that are written ... */
+    uint32_t width[3];     /* ... samples a row of each component it carries (packed: luma samples) ... */
+    uint32_t height[3];    /* ... and rows; unused planes are all zero */
+} compeg_planes_layout;    /* 88 bytes */
+/* No device needed: one image's layout for a width x height image of `components` components (3, or 1: grayscale)
+ * whose luma is sampled hsample x vsample (compeg_image_sampling).  COMPEG_E_INVALID_ARG for: NULL arguments, a
+ * format or chroma value out of range, nonzero reserved words, CHROMA_420 with a packed format, a pitch below the
+ * row's bytes (the message names both), a zero extent, a sampling that is none of the five;
+ * COMPEG_E_UNSUPPORTED for a packed format or CHROMA_420 on anything but 4:2:2.  Nothing is written on failure. */
+int compeg_planes_shape(const compeg_planes_spec *spec, uint32_t width, uint32_t height, uint32_t components, uint32_t hsample,
+                        uint32_t vsample, compeg_planes_layout *layout);
+/* The images of the batch's last upload, image i to device_dst + i * total_bytes.  All images must have one size and one
+ * sampling (COMPEG_E_INVALID_ARG with a message otherwise, as compeg_batch_pack_tensor asks for one size); dst_bytes
+ * below count * total_bytes is refused before anything is launched (the message names both numbers).  Records on
+ * hip_stream (NULL = the gpu's stream) and returns without waiting; compeg_batch_wait covers it.  compeg_batch_set_chunk
+ * and the three preprocessing modes work as for compeg_batch_decode.  Any number of calls, with different specs, in any
+ * order with compeg_batch_decode, after one upload.  It records none of the batch's timing events.  Ordering is the
+ * tensor packs': a planes decode on another stream than the batch's previous work waits for that work, and what the
+ * batch does next on another stream waits for it.  compeg_batch_last_kernel then says COMPEG_KERNEL_PLANES.
+ * Known limits: a lane per restart interval on every launch (no cooperative, walk or streamed-window form: a single
+ * frame or long intervals decode slowly); no mixed sizes or samplings; no resampling but CHROMA_420 from 4:2:2. */
+int compeg_batch_decode_planes(compeg_batch *batch, const compeg_planes_spec *spec, void *device_dst, size_t dst_bytes,
+                               void *hip_stream);
+/* One image: uploads and preprocesses as compeg_decoder_enqueue does (host or device preprocessing), records the planes
+ * decode on hip_stream (NULL = the gpu's stream) and returns without waiting.  The decoder's texture, its extent and
+ * what the packs read stay those of the last RGBA decode; compeg_decoder_read_coefficients afterwards speaks of this
+ * image.  To wait: synchronise hip_stream, or call compeg_decoder_decode_planes_blocking, which does.  The decoder's
+ * next enqueue or pack on another stream waits for the planes decode, as this call waits for the decoder's previous
+ * work.  compeg_decoder_last_kernel then says COMPEG_KERNEL_PLANES. */
+int compeg_decoder_decode_planes(compeg_decoder *dec, const compeg_image *img, const compeg_planes_spec *spec, void *device_dst,
+                                 size_t dst_bytes, void *hip_stream);
+int compeg_decoder_decode_planes_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_planes_spec *spec,
+                                          void *device_dst, size_t dst_bytes);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -104,6 +104,32 @@ pub struct compeg_luma_spec {
     pub reserved: u32,
 }
 
+/// What a planes decode writes (compeg_hip.h, "Planar YCbCr output"): the format, the chroma option and the two pitches
+/// in bytes (0 = tight).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct compeg_planes_spec {
+    pub format: u32,
+    pub chroma: u32,
+    pub luma_pitch: u32,
+    pub chroma_pitch: u32,
+    pub reserved: [u32; 4],
+}
+
+/// Where one image's planes lie (`compeg_planes_shape`): offsets, pitches, row bytes and extents per plane.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct compeg_planes_layout {
+    pub planes: u32,
+    pub reserved: u32,
+    pub total_bytes: u64,
+    pub offset: [u64; 3],
+    pub pitch: [u32; 3],
+    pub row_bytes: [u32; 3],
+    pub width: [u32; 3],
+    pub height: [u32; 3],
+}
+
 pub const COMPEG_OK: c_int = 0;
 pub const COMPEG_E_INVALID_ARG: c_int = -1;
 pub const COMPEG_E_UNSUPPORTED: c_int = -2;
@@ -122,6 +148,13 @@ pub const COMPEG_KERNEL_SPLIT: c_int = 5;
 pub const COMPEG_KERNEL_FUSED_LAYOUT: c_int = 6;
 pub const COMPEG_KERNEL_FUSED_STREAM: c_int = 7;
 pub const COMPEG_KERNEL_WALK_MCU: c_int = 8;
+pub const COMPEG_KERNEL_PLANES: c_int = 9;
+pub const COMPEG_PLANES_PLANAR: u32 = 0;
+pub const COMPEG_PLANES_SEMIPLANAR: u32 = 1;
+pub const COMPEG_PLANES_YUYV: u32 = 2;
+pub const COMPEG_PLANES_UYVY: u32 = 3;
+pub const COMPEG_CHROMA_AS_CODED: u32 = 0;
+pub const COMPEG_CHROMA_420: u32 = 1;
 pub const COMPEG_TENSOR_U8: u32 = 0;
 pub const COMPEG_TENSOR_F16: u32 = 1;
 pub const COMPEG_TENSOR_BF16: u32 = 2;
@@ -162,6 +195,7 @@ extern "C" {
     pub fn compeg_image_height(img: *const compeg_image) -> u32;
     pub fn compeg_image_parallelism(img: *const compeg_image) -> u32;
     pub fn compeg_image_components(img: *const compeg_image) -> u32;
+    pub fn compeg_image_sampling(img: *const compeg_image, hsample: *mut u32, vsample: *mut u32) -> c_int;
     pub fn compeg_image_metadata(img: *const compeg_image) -> *const u8;
     pub fn compeg_image_huffman_l1(img: *const compeg_image) -> *const u8;
     pub fn compeg_image_huffman_l2(img: *const compeg_image, nbytes: *mut usize) -> *const u8;
@@ -323,4 +357,14 @@ extern "C" {
                                          luma: *const compeg_luma_spec, regions: *const compeg_oriented_region, count: usize,
                                          pad: *const float, device_dst: *mut c_void, dst_bytes: usize,
                                          hip_stream: *mut c_void) -> c_int;
+
+    // Planar YCbCr output (extension)
+    pub fn compeg_planes_shape(spec: *const compeg_planes_spec, width: u32, height: u32, components: u32, hsample: u32, vsample: u32,
+                               layout: *mut compeg_planes_layout) -> c_int;
+    pub fn compeg_batch_decode_planes(batch: *mut compeg_batch, spec: *const compeg_planes_spec, device_dst: *mut c_void,
+                                      dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_decoder_decode_planes(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_planes_spec,
+                                        device_dst: *mut c_void, dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_decoder_decode_planes_blocking(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_planes_spec,
+                                                 device_dst: *mut c_void, dst_bytes: usize) -> c_int;
 }

@@ -337,6 +337,53 @@ impl NhwcSpec {
     }
 }
 
+/// The format of a planes decode (compeg_hip.h, "Planar YCbCr output").
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum PlanesFormat {
+    /// Y, then Cb, then Cr: I422 / I444 / I440 / I420 / Y800 by the file's sampling.
+    Planar,
+    /// Y, then interleaved Cb Cr pairs: NV16 / NV24 / NV12.
+    Semiplanar,
+    /// One packed plane, 4:2:2 files only.
+    Yuyv,
+    Uyvy,
+}
+
+/// What `Decoder::decode_planes` / `Batch::decode_planes` write: the format, whether 4:2:2 chroma is averaged to 4:2:0
+/// (planar and semiplanar formats, 4:2:2 files only), and the row pitches in bytes (0 = tight).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct PlanesSpec {
+    pub format: PlanesFormat,
+    pub chroma_420: bool,
+    pub luma_pitch: u32,
+    pub chroma_pitch: u32,
+}
+
+impl PlanesSpec {
+    pub fn new(format: PlanesFormat) -> Self {
+        PlanesSpec { format, chroma_420: false, luma_pitch: 0, chroma_pitch: 0 }
+    }
+
+    fn raw(&self) -> ffi::compeg_planes_spec {
+        let format = match self.format {
+            PlanesFormat::Planar => ffi::COMPEG_PLANES_PLANAR,
+            PlanesFormat::Semiplanar => ffi::COMPEG_PLANES_SEMIPLANAR,
+            PlanesFormat::Yuyv => ffi::COMPEG_PLANES_YUYV,
+            PlanesFormat::Uyvy => ffi::COMPEG_PLANES_UYVY,
+        };
+        let chroma = if self.chroma_420 { ffi::COMPEG_CHROMA_420 } else { ffi::COMPEG_CHROMA_AS_CODED };
+        ffi::compeg_planes_spec { format, chroma, luma_pitch: self.luma_pitch, chroma_pitch: self.chroma_pitch, reserved: [0; 4] }
+    }
+}
+
+/// No device needed: one image's planes for a `width x height` image of `components` components (3, or 1: grayscale)
+/// whose luma is sampled `sampling` (`ImageData::sampling`).
+pub fn planes_shape(spec: &PlanesSpec, width: u32, height: u32, components: u32, sampling: (u32, u32)) -> Result<ffi::compeg_planes_layout> {
+    let mut layout = ffi::compeg_planes_layout::default();
+    check(unsafe { ffi::compeg_planes_shape(&spec.raw(), width, height, components, sampling.0, sampling.1, &mut layout) })?;
+    Ok(layout)
+}
+
 /// The weights of `Decoder::pack_tensor_luma` / `Batch::pack_tensor_luma` (compeg_hip.h, "Luma tensor output"): per source
 /// pixel `L = (wR R + wG G + wB B + 32768) >> 16`; the destination is `[count][1][oh][ow]`.  A grayscale frame gives its
 /// own values under any of them.
@@ -487,6 +534,14 @@ impl<'a> ImageData<'a> {
     /// Extension: components of the frame -- 3, or 1 for a grayscale image (`ParseFlags::grayscale`).
     pub fn components(&self) -> u32 {
         unsafe { ffi::compeg_image_components(self.raw.as_ptr()) }
+    }
+
+    /// Extension: the luma component's sampling factors (h, v) -- (2, 1) for 4:2:2, (1, 1) for 4:4:4 and grayscale,
+    /// (1, 2) for 4:4:0, (2, 2) for 4:2:0: what `planes_shape` sizes the planes with.
+    pub fn sampling(&self) -> (u32, u32) {
+        let (mut h, mut v) = (0, 0);
+        unsafe { ffi::compeg_image_sampling(self.raw.as_ptr(), &mut h, &mut v) };
+        (h, v)
     }
 
     /// Extension: the file's EXIF orientation tag, 1..8; 1 where it has no usable one.
@@ -704,6 +759,27 @@ impl Decoder {
         let pad = pad.as_ref().map_or(ptr::null(), |p| p as *const f32);
         check(ffi::compeg_decoder_pack_tensor_luma(self.raw.as_ptr(), &spec.raw(), &filter.raw(), &luma.raw(), raw.as_ptr(), raw.len(), pad,
                                                    device_dst, dst_bytes, stream.0))
+    }
+
+    /// Extension: uploads and preprocesses `image` as `enqueue` does and records a decode that writes the file's own
+    /// Y, Cb and Cr samples into caller-owned device memory as `planes_shape` lays them out -- no colour step, no
+    /// upsampling.  The texture and what the packs read are not touched.  Returns without waiting: synchronise `stream`,
+    /// or use `decode_planes_blocking`.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn decode_planes(&mut self, image: &ImageData, spec: &PlanesSpec, device_dst: *mut c_void, dst_bytes: usize,
+                                stream: Stream) -> Result<()> {
+        check(ffi::compeg_decoder_decode_planes(self.raw.as_ptr(), image.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
+    }
+
+    /// `decode_planes` on the gpu's own stream, and the wait for it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes.
+    pub unsafe fn decode_planes_blocking(&mut self, image: &ImageData, spec: &PlanesSpec, device_dst: *mut c_void,
+                                         dst_bytes: usize) -> Result<()> {
+        check(ffi::compeg_decoder_decode_planes_blocking(self.raw.as_ptr(), image.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes))
     }
 
     /// Test helper (the reference's tests copy the texture to a buffer): waits and
@@ -945,6 +1021,16 @@ impl Batch {
         let pad = pad.as_ref().map_or(ptr::null(), |p| p as *const f32);
         check(ffi::compeg_batch_pack_tensor_luma(self.raw.as_ptr(), &spec.raw(), &filter.raw(), &luma.raw(), raw.as_ptr(), raw.len(), pad,
                                                  device_dst, dst_bytes, stream.0))
+    }
+
+    /// Extension: records a decode of the last upload's images (all of one size and sampling) that writes each one's own
+    /// Y, Cb and Cr samples into caller-owned device memory, image i at `i * total_bytes` of `planes_shape`.  The RGBA
+    /// outputs are not touched.  Returns without waiting; `wait` covers it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn decode_planes(&mut self, spec: &PlanesSpec, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        check(ffi::compeg_batch_decode_planes(self.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
     }
 
     /// The EXIF orientation tag (1..8) of image `index` of the last upload.
