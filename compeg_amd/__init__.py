@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
-                   LIB_PATH, METADATA_BYTES, Error, FilterSpec, LumaSpec, NhwcSpec, OrientedRegion, PlanesLayout, PlanesSpec, Rect, Region, ResizeSpec,
+                   LIB_PATH, METADATA_BYTES, Error, FilterSpec, LumaSpec, NhwcSpec, OrientedRegion, PlanesLayout, PlanesSpec, Rect, ReducedSpec, Region, ResizeSpec,
                    TensorSpec, check,
                    lib)
 
@@ -27,11 +27,15 @@ __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Te
            "resized_tensor_shape", "RESIZE_FILTERS", "ResizeSpec", "Rect", "Region", "FIT_ALIGNS", "region_fit",
            "region_tensor_shape", "FILTER_KERNELS", "FilterSpec", "filtered_tensor_shape", "ORIENTATIONS", "OrientedRegion",
            "orient_rect", "oriented_tensor_shape", "NhwcSpec", "nhwc_tensor_shape", "LumaSpec", "LUMA_WEIGHTS",
-           "luma_tensor_shape", "PlanesSpec", "PlanesLayout", "PLANES_FORMATS", "PLANES_CHROMA", "planes_shape"]
+           "luma_tensor_shape", "PlanesSpec", "PlanesLayout", "PLANES_FORMATS", "PLANES_CHROMA", "planes_shape",
+           "ReducedSpec", "REDUCED_FORMATS", "reduced_shape"]
 
 
-# compeg_decoder_last_kernel / compeg_batch_last_kernel (include/compeg_hip.h: COMPEG_KERNEL_*)
+# compeg_decoder_last_kernel / compeg_batch_last_kernel (include/compeg_hip.h: COMPEG_KERNEL_*).  KERNEL_NAMES: the RGBA
+# routes and the planes decode, ten names (tests/test_planes_stream.py pins the count); ALL_KERNEL_NAMES: every value
+# last_kernel() can give, the reduced decode's (COMPEG_KERNEL_REDUCED = 10) behind them.
 KERNEL_NAMES = ("none", "fused", "pair", "coop_team", "generic", "split", "fused_layout", "fused_stream", "walk_mcu", "planes")
+ALL_KERNEL_NAMES = KERNEL_NAMES + ("reduced",)
 
 
 def version():
@@ -440,6 +444,31 @@ def planes_shape(width, height, sampling=(2, 1), components=3, format="planar", 
     return planes, lay.total_bytes
 
 
+# Reduced-size decode (include/compeg_hip.h: COMPEG_REDUCED_*): formats by name
+REDUCED_FORMATS = {"rgba": 0, "rgb_planar": 1}
+
+
+def _reduced_spec(format, pitch, denominator=8):
+    """compeg_reduced_spec from a name (or the header's number, which the library checks); pitch: None or 0 = tight."""
+    if isinstance(format, str) and format not in REDUCED_FORMATS:
+        raise Error(f"unknown reduced format {format!r} (one of {', '.join(REDUCED_FORMATS)})")
+    spec = ReducedSpec()
+    spec.denominator = denominator
+    spec.format = REDUCED_FORMATS[format] if isinstance(format, str) else format
+    spec.pitch = int(pitch or 0)
+    return spec
+
+
+def reduced_shape(width, height, format="rgba", pitch=None):
+    """(ow, oh, pitch, total_bytes) of the 1/8-scale decode of one width x height image -- compeg_reduced_shape; no
+    device needed.  ow x oh = ceil(width / 8) x ceil(height / 8); "rgba": rows of 4 ow bytes at `pitch` (a multiple of 4,
+    None = tight); "rgb_planar": a tight [3, oh, ow] u8 block."""
+    spec = _reduced_spec(format, pitch)
+    ow, oh, pt, total = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+    check(lib.compeg_reduced_shape(C.byref(spec), width, height, C.byref(ow), C.byref(oh), C.byref(pt), C.byref(total)))
+    return ow.value, oh.value, pt.value, total.value
+
+
 def _host_view(data):
     a = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
     return np.ascontiguousarray(a)
@@ -732,6 +761,22 @@ class Decoder:
         else:
             check(lib.compeg_decoder_decode_planes(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
 
+    def decode_reduced(self, data, dst, format="rgba", pitch=None, hip_stream=0, blocking=False):
+        """Extension (compeg_decoder_decode_reduced): uploads and preprocesses `data` as enqueue does and records, on
+        hip_stream (0 = the gpu's stream), a decode at 1/8 scale -- one RGB pixel per luma data unit, from the DC terms
+        alone -- into caller-owned device memory as reduced_shape lays it out.  It is pixel (8x, 8y) of the full decode
+        with every AC coefficient zero, not the 8 x 8 mean of the full decode.  dst: (address, nbytes), a tensor, or a
+        __cuda_array_interface__ object of at least total_bytes.  The texture and what the packs read are not touched.
+        Returns without waiting; blocking=True (the gpu's stream only) waits for the decode."""
+        spec = _reduced_spec(format, pitch)
+        addr, nbytes = _device_range(dst)
+        if blocking:
+            if hip_stream:
+                raise Error("decode_reduced: blocking=True records on the gpu's own stream")
+            check(lib.compeg_decoder_decode_reduced_blocking(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes))
+        else:
+            check(lib.compeg_decoder_decode_reduced(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
+
     def last_warning(self):
         return lib.compeg_decoder_last_warning(self._h).decode()
 
@@ -744,7 +789,7 @@ class Decoder:
 
     def last_kernel(self):
         """Diagnostics: the decode kernel the last enqueue went to (KERNEL_* names)."""
-        return KERNEL_NAMES[lib.compeg_decoder_last_kernel(self._h)]
+        return ALL_KERNEL_NAMES[lib.compeg_decoder_last_kernel(self._h)]
 
     def set_device_preprocess(self, on=True):
         """Extension: preprocess scans with the device-side scan kernels instead of on the host."""
@@ -931,6 +976,15 @@ class Batch:
         addr, nbytes = _device_range(dst)
         check(lib.compeg_batch_decode_planes(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
 
+    def decode_reduced(self, dst, format="rgba", pitch=None, hip_stream=0):
+        """Extension (compeg_batch_decode_reduced): records, on hip_stream (0 = the gpu's stream), a decode of the last
+        upload's images (all of one size and sampling) at 1/8 scale into caller-owned device memory, image i at
+        i * total_bytes of reduced_shape.  dst: (address, nbytes), a tensor, or a __cuda_array_interface__ object.  The
+        RGBA outputs are not touched; wait() covers it."""
+        spec = _reduced_spec(format, pitch)
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_batch_decode_reduced(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
+
     def wait(self):
         check(lib.compeg_batch_wait(self._h))
 
@@ -1054,7 +1108,7 @@ class Batch:
 
     def last_kernel(self):
         """Diagnostics: the decode kernel the first launch of the last decode went to (KERNEL_NAMES)."""
-        return KERNEL_NAMES[lib.compeg_batch_last_kernel(self._h)]
+        return ALL_KERNEL_NAMES[lib.compeg_batch_last_kernel(self._h)]
 
     def set_timing(self, on=True):
         """compeg_batch_set_timing: off = decodes record no timing events (they run closer together)."""

@@ -78,6 +78,11 @@ class PlanesLayout(C.Structure):
                 ("pitch", C.c_uint32 * 3), ("row_bytes", C.c_uint32 * 3), ("width", C.c_uint32 * 3), ("height", C.c_uint32 * 3)]
 
 
+class ReducedSpec(C.Structure):
+    """compeg_reduced_spec (include/compeg_hip.h, "Reduced-size decode"): the scale's denominator (8), format, RGBA pitch."""
+    _fields_ = [("denominator", C.c_uint32), ("format", C.c_uint32), ("pitch", C.c_uint32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -185,6 +190,10 @@ def _load():
         "compeg_batch_decode_planes": (i, [vp, C.POINTER(PlanesSpec), vp, sz, vp]),
         "compeg_decoder_decode_planes": (i, [vp, vp, C.POINTER(PlanesSpec), vp, sz, vp]),
         "compeg_decoder_decode_planes_blocking": (i, [vp, vp, C.POINTER(PlanesSpec), vp, sz]),
+        "compeg_reduced_shape": (i, [C.POINTER(ReducedSpec), u32, u32, pu32, pu32, pu32, C.POINTER(C.c_uint64)]),
+        "compeg_batch_decode_reduced": (i, [vp, C.POINTER(ReducedSpec), vp, sz, vp]),
+        "compeg_decoder_decode_reduced": (i, [vp, vp, C.POINTER(ReducedSpec), vp, sz, vp]),
+        "compeg_decoder_decode_reduced_blocking": (i, [vp, vp, C.POINTER(ReducedSpec), vp, sz]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("COMPEG_LIB") and not hasattr(L, name):

@@ -1996,3 +1996,172 @@ int compeg_decoder_decode_planes_blocking(compeg_decoder *dec, const compeg_imag
 }
 
 } // extern "C"
+
+/* ---- Reduced-size decode ---------------------------------------------------- */
+
+namespace {
+
+struct ReducedLayout {
+    uint32_t ow, oh, pitch;
+    uint64_t total;
+};
+
+// compeg_reduced_spec as the header has it, laid out for a width x height image: 0 with *out filled in, or the error
+// recorded.  (The texts name values, not the header's macros.)
+int reduced_layout(const compeg_reduced_spec *spec, uint32_t width, uint32_t height, ReducedLayout *out)
+{
+    if (!spec)
+        return fail(COMPEG_E_INVALID_ARG, "spec is NULL");
+    if (spec->denominator != 8u)
+        return fail(COMPEG_E_INVALID_ARG, ("reduced spec: denominator " + std::to_string(spec->denominator) +
+                                           " is not 8: 1/8 is the DC-only decode and the only one built").c_str());
+    if (spec->format > COMPEG_REDUCED_RGB_PLANAR)
+        return fail(COMPEG_E_INVALID_ARG, ("reduced spec: format " + std::to_string(spec->format) + " is neither 0 (rgba) nor 1 (rgb planar)").c_str());
+    if (width == 0 || height == 0)
+        return fail(COMPEG_E_INVALID_ARG, "reduced: the image has no pixels");
+    ReducedLayout l;
+    l.ow = (width - 1u) / 8u + 1u;
+    l.oh = (height - 1u) / 8u + 1u;
+    if (spec->format == COMPEG_REDUCED_RGB_PLANAR) {
+        if (spec->pitch != 0u)
+            return fail(COMPEG_E_INVALID_ARG, ("reduced spec: pitch " + std::to_string(spec->pitch) + " with the planar format, whose rows are tight (pitch 0)").c_str());
+        l.pitch = l.ow;
+        l.total = 3ull * l.ow * l.oh;
+    } else {
+        const uint64_t row = 4ull * l.ow;
+        if (spec->pitch != 0u && (spec->pitch < row || spec->pitch % 4u != 0u))
+            return fail(COMPEG_E_INVALID_ARG, ("reduced spec: pitch " + std::to_string(spec->pitch) + " is not a multiple of 4 at or above the row's " +
+                                               std::to_string(row) + " bytes").c_str());
+        l.pitch = spec->pitch ? spec->pitch : uint32_t(row);
+        l.total = uint64_t(l.pitch) * l.oh;
+    }
+    *out = l;
+    return COMPEG_OK;
+}
+
+int check_reduced_destination(const compeg_reduced_spec &spec, const void *device_dst, size_t dst_bytes, uint64_t total, size_t images)
+{
+    if (!device_dst)
+        return fail(COMPEG_E_INVALID_ARG, "device_dst is NULL");
+    if (spec.format == COMPEG_REDUCED_RGBA && reinterpret_cast<uintptr_t>(device_dst) % 4u != 0u)
+        return fail(COMPEG_E_INVALID_ARG, "reduced: the rgba destination's address is not a multiple of 4");
+    if (uint64_t(dst_bytes) / total < images)
+        return fail(COMPEG_E_INVALID_ARG, ("reduced: dst_bytes is " + std::to_string(dst_bytes) + ", " + std::to_string(images) + " image(s) of " +
+                                           std::to_string(total) + " bytes need " + std::to_string(total * images)).c_str());
+    return COMPEG_OK;
+}
+
+ReducedTarget reduced_target(const compeg_reduced_spec &spec, const ReducedLayout &l, void *device_dst)
+{
+    ReducedTarget t{};
+    t.dst = static_cast<uint8_t *>(device_dst);
+    t.image_stride = l.total;
+    t.ow = l.ow;
+    t.oh = l.oh;
+    t.pitch = l.pitch;
+    t.format = spec.format;
+    return t;
+}
+
+int decoder_reduced(compeg_decoder *dec, const compeg_image *img, const compeg_reduced_spec *spec, void *device_dst, size_t dst_bytes,
+                    hipStream_t stream)
+{
+    const ImageData &data = *img->data;
+    ReducedLayout l;
+    int rc = reduced_layout(spec, data.width, data.height, &l);
+    if (rc == COMPEG_OK)
+        rc = check_reduced_destination(*spec, device_dst, dst_bytes, l.total, 1);
+    if (rc != COMPEG_OK)
+        return rc;
+    const ReducedTarget target = reduced_target(*spec, l, device_dst);
+    Status s = dec->enqueue(data, stream, nullptr, false, nullptr, &target);
+    return s.ok() ? ok() : fail(s);
+}
+
+} // namespace
+
+extern "C" {
+
+int compeg_reduced_shape(const compeg_reduced_spec *spec, uint32_t width, uint32_t height, uint32_t *out_width, uint32_t *out_height,
+                         uint32_t *pitch, uint64_t *total_bytes)
+{
+    return guarded([&] {
+        ReducedLayout l;
+        const int rc = reduced_layout(spec, width, height, &l);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (out_width)
+            *out_width = l.ow;
+        if (out_height)
+            *out_height = l.oh;
+        if (pitch)
+            *pitch = l.pitch;
+        if (total_bytes)
+            *total_bytes = l.total;
+        return ok();
+    });
+}
+
+int compeg_batch_decode_reduced(compeg_batch *batch, const compeg_reduced_spec *spec, void *device_dst, size_t dst_bytes, void *hip_stream)
+{
+    return guarded([&] {
+        if (!batch)
+            return fail(COMPEG_E_INVALID_ARG, null_text(batch));
+        if (!spec)
+            return fail(COMPEG_E_INVALID_ARG, "spec is NULL");
+        Status s = batch->finish_upload(); // (the descriptors looked at below are the finished upload's)
+        if (!s.ok())
+            return fail(s);
+        if (batch->count == 0)
+            return fail(COMPEG_E_INVALID_ARG, "reduced: nothing uploaded yet");
+        const ImageDesc &first = batch->descs[0];
+        const uint32_t comps0 = first.dus_per_mcu == 1 ? 1u : 3u;
+        for (size_t i = 1; i < batch->count; i++) {
+            const ImageDesc &d = batch->descs[i];
+            if (d.out_w != first.out_w || d.out_h != first.out_h)
+                return fail(COMPEG_E_INVALID_ARG, ("reduced: the batch's images are not all of one size (image " + std::to_string(i) + " is " +
+                                                   std::to_string(d.out_w) + "x" + std::to_string(d.out_h) + ", image 0 " + std::to_string(first.out_w) + "x" +
+                                                   std::to_string(first.out_h) + ")").c_str());
+            const uint32_t comps = d.dus_per_mcu == 1 ? 1u : 3u;
+            if (comps != comps0 || d.hsample[0] != first.hsample[0] || d.vsample[0] != first.vsample[0])
+                return fail(COMPEG_E_INVALID_ARG, (std::string("reduced: the batch's images are not all of one sampling (image ") + std::to_string(i) + " is " +
+                                                   sampling_name(comps, d.hsample[0], d.vsample[0]) + ", image 0 " +
+                                                   sampling_name(comps0, first.hsample[0], first.vsample[0]) + ")").c_str());
+        }
+        ReducedLayout l;
+        int rc = reduced_layout(spec, first.out_w, first.out_h, &l);
+        if (rc == COMPEG_OK)
+            rc = check_reduced_destination(*spec, device_dst, dst_bytes, l.total, batch->count);
+        if (rc != COMPEG_OK)
+            return rc;
+        s = batch->decode_reduced(reduced_target(*spec, l, device_dst), first.hsample[0], comps0 == 1 ? 0u : first.vsample[0],
+                                  stream_of(*batch, hip_stream));
+        return s.ok() ? ok() : fail(s);
+    });
+}
+
+int compeg_decoder_decode_reduced(compeg_decoder *dec, const compeg_image *img, const compeg_reduced_spec *spec, void *device_dst,
+                                  size_t dst_bytes, void *hip_stream)
+{
+    return guarded([&] {
+        if (!dec || !img)
+            return fail(COMPEG_E_INVALID_ARG, "NULL argument");
+        return decoder_reduced(dec, img, spec, device_dst, dst_bytes, stream_of(*dec, hip_stream));
+    });
+}
+
+int compeg_decoder_decode_reduced_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_reduced_spec *spec, void *device_dst,
+                                           size_t dst_bytes)
+{
+    return guarded([&] {
+        if (!dec || !img)
+            return fail(COMPEG_E_INVALID_ARG, "NULL argument");
+        const int rc = decoder_reduced(dec, img, spec, device_dst, dst_bytes, dec->gpu->stream);
+        if (rc != COMPEG_OK)
+            return rc;
+        const hipError_t e = hipStreamSynchronize(dec->gpu->stream);
+        return e == hipSuccess ? ok() : fail(hip_status(e, "hipStreamSynchronize"));
+    });
+}
+
+} // extern "C"

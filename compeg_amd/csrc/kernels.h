@@ -8,6 +8,7 @@
 #include "compeg_hip.h"
 #include "device_types.h"
 #include "planes_types.h"
+#include "reduced_types.h"
 #include "region_types.h"
 
 namespace compeg {
@@ -201,6 +202,14 @@ hipError_t launch_luma_tensor(const void *device_blob, size_t tables_at, uint32_
 uint32_t planes_wave_cap(uint32_t hs, uint32_t vs);
 hipError_t launch_planes(const ImageDesc *descs, uint32_t images, uint32_t max_intervals, const HuffLdsPlan &plan, uint32_t hs, uint32_t vs,
                          const PlanesTarget &target, hipStream_t stream);
+
+// Reduced decode (reduced_kernels.hip, reduced_body.h): the images at 1/8 scale, one RGB pixel per luma data unit from
+// the DC terms alone, into the caller's memory as `target` lays it out; a lane per restart interval behind whole
+// windows.  hs x vs as for launch_planes; plan: plan_huffman's with fused = false (the entropy walk's occupancy) and
+// wave_cap = reduced_wave_cap.  target: validated by the caller.
+uint32_t reduced_wave_cap();
+hipError_t launch_reduced(const ImageDesc *descs, uint32_t images, uint32_t max_intervals, const HuffLdsPlan &plan, uint32_t hs, uint32_t vs,
+                          const ReducedTarget &target, hipStream_t stream);
 
 #if defined(CG_AC_STAMPS)
 // diagnostic build: AC-loop cycle counters (kernels_body.h)

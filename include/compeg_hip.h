@@ -200,6 +200,8 @@ int compeg_decoder_last_stage_times(const compeg_decoder *dec, compeg_stage_time
                                        take or takes less well: beyond 256 MCUs, no DRI at all, a 4K frame's 1080 teams) */
 #define COMPEG_KERNEL_PLANES 9       /* decode_planes_422 / _444 / _440 / _420 / _gray_kernel: a planes decode
                                        (compeg_*_decode_planes), a lane per restart interval */
+#define COMPEG_KERNEL_REDUCED 10     /* decode_reduced_422 / _444 / _440 / _420 / _gray_kernel: a reduced decode
+                                       (compeg_*_decode_reduced), a lane per restart interval */
 int compeg_decoder_last_kernel(const compeg_decoder *dec);
 /* Extension: on != 0 moves the scan preprocessing of every following decode
  * from the host (the reference's data flow, default) to the device-side scan
@@ -799,6 +801,76 @@ int compeg_decoder_decode_planes(compeg_decoder *dec, const compeg_image *img, c
                                  size_t dst_bytes, void *hip_stream);
 int compeg_decoder_decode_planes_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_planes_spec *spec,
                                           void *device_dst, size_t dst_bytes);
+
+/* ---- Reduced-size decode (extension) ------------------------------------------
+ * A third kind of decode: the image at 1/8 scale, one RGB pixel per 8 x 8 luma data unit, made from the DC terms alone
+ * -- the entropy decode and nothing of the transform -- and written into caller-owned device memory.  What libjpeg
+ * calls scale_denom = 8: thumbnails, motion grids, small model inputs, without a full-size image in between.  New
+ * entry points beside the old ones: the RGBA output, compeg_decoder_output / _read_output, and what the tensor packs
+ * see as "the last decode" are not touched by a reduced decode, and without these calls nothing behaves differently.
+ *
+ * Reduced extent: ow = ceil(W / 8), oh = ceil(H / 8).
+ *
+ * One sample per data unit.  dc is the data unit's prediction-summed, dequantised DC term with 32-bit wrap, exactly
+ * what every other decode feeds its transform (the entropy quirks unless COMPEG_PARSE_STANDARD_ENTROPY, the wrapping
+ * predictor, DC categories above 15 all act as they do there).  The sample is
+ *     s = trunc(clamp((float(dc) * 0.125f) + 128.5f, 0, 255))
+ * -- one f32 product, one f32 sum, a clamp to 0..255, a truncation.  This is what the decoder's transform leaves in all
+ * 64 samples of a data unit whose AC coefficients are zero.
+ *
+ * Pixel (x, y) of the reduced image.  Y comes from luma data unit (x, y) of the luma grid, Cb and Cr from chroma data
+ * unit (x / hs, y / vs) -- nearest neighbour, as the full decode replicates chroma -- and the colour step is the full
+ * decode's integer YCbCr -> RGB with A = 255.  For grayscale files R = G = B = s.  Equivalently: pixel (8 x, 8 y) of
+ * the full decode of the same file with every AC coefficient set to zero.  It is NOT the mean of the full decode's
+ * 8 x 8 block: the colour step clamps per pixel, and the mean of clamped values is not the clamped mean.
+ *
+ * MCUs behind the last complete restart interval are not decoded and their bytes in the destination are NOT WRITTEN:
+ * the memory is the caller's, its previous contents stay.  Nothing outside ow x oh is ever written -- not the rest of
+ * a row inside its pitch, not a row below the last; an MCU the reduced extent cuts is stored in part.
+ *
+ * format:
+ *   RGBA        interleaved R G B A, 4 bytes a pixel, A = 255.  pitch: bytes from row to row, 0 = tight (4 ow).  The
+ *               destination's address and the pitch must be multiples of 4 (COMPEG_E_INVALID_ARG otherwise).
+ *   RGB_PLANAR  [3, oh, ow] bytes, tight, any address: a CHW u8 tensor as it stands.  pitch must be 0.
+ * denominator must be 8: 1/8 is the DC-only decode and the only one built (COMPEG_E_INVALID_ARG for any other value). */
+#define COMPEG_REDUCED_RGBA 0
+#define COMPEG_REDUCED_RGB_PLANAR 1
+typedef struct compeg_reduced_spec {
+    uint32_t denominator; /* 8 */
+    uint32_t format;      /* COMPEG_REDUCED_* */
+    uint32_t pitch;       /* RGBA: bytes from row to row, 0 = tight; RGB_PLANAR: 0 */
+} compeg_reduced_spec;    /* 12 bytes */
+/* No device needed: the reduced extent of a width x height image, the pitch that will be used (RGB_PLANAR: ow) and one
+ * image's bytes (RGBA: pitch * oh, the last row at its full pitch; RGB_PLANAR: 3 * ow * oh).  Any output may be NULL.
+ * COMPEG_E_INVALID_ARG for: a NULL spec, a denominator other than 8, a format out of range, RGB_PLANAR with a pitch,
+ * an RGBA pitch below 4 * ow or not a multiple of 4 (the message names both), a zero extent.  Nothing is written on
+ * failure. */
+int compeg_reduced_shape(const compeg_reduced_spec *spec, uint32_t width, uint32_t height, uint32_t *out_width,
+                         uint32_t *out_height, uint32_t *pitch, uint64_t *total_bytes);
+/* The images of the batch's last upload, image i to device_dst + i * total_bytes.  All images must have one size and one
+ * sampling (COMPEG_E_INVALID_ARG with a message otherwise, as compeg_batch_decode_planes asks); dst_bytes below
+ * count * total_bytes is refused before anything is launched (the message names both numbers).  Records on hip_stream
+ * (NULL = the gpu's stream) and returns without waiting; compeg_batch_wait covers it.  compeg_batch_set_chunk and the
+ * three preprocessing modes work as for compeg_batch_decode.  Any number of calls, with different specs, in any order
+ * with compeg_batch_decode and compeg_batch_decode_planes, after one upload.  It records none of the batch's timing
+ * events.  Ordering is the tensor packs': a reduced decode on another stream than the batch's previous work waits for
+ * that work, and what the batch does next on another stream waits for it.  compeg_batch_last_kernel then says
+ * COMPEG_KERNEL_REDUCED.
+ * Known limits: a lane per restart interval on every launch (no cooperative, walk or streamed-window form: a single
+ * frame or long intervals decode slowly); no mixed sizes or samplings; 1/8 only; the tensor packs do not read a
+ * caller's image. */
+int compeg_batch_decode_reduced(compeg_batch *batch, const compeg_reduced_spec *spec, void *device_dst, size_t dst_bytes,
+                                void *hip_stream);
+/* One image: uploads and preprocesses as compeg_decoder_enqueue does (host or device preprocessing), records the
+ * reduced decode on hip_stream (NULL = the gpu's stream) and returns without waiting.  The decoder's texture, its
+ * extent and what the packs read stay those of the last RGBA decode.  To wait: synchronise hip_stream, or call
+ * compeg_decoder_decode_reduced_blocking, which does.  The decoder's next enqueue or pack on another stream waits for
+ * the reduced decode, as this call waits for the decoder's previous work.  compeg_decoder_last_kernel then says
+ * COMPEG_KERNEL_REDUCED. */
+int compeg_decoder_decode_reduced(compeg_decoder *dec, const compeg_image *img, const compeg_reduced_spec *spec, void *device_dst,
+                                  size_t dst_bytes, void *hip_stream);
+int compeg_decoder_decode_reduced_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_reduced_spec *spec,
+                                           void *device_dst, size_t dst_bytes);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -130,6 +130,16 @@ pub struct compeg_planes_layout {
     pub height: [u32; 3],
 }
 
+/// What a reduced decode writes (compeg_hip.h, "Reduced-size decode"): the scale's denominator (8), the format and the
+/// RGBA row pitch in bytes (0 = tight).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct compeg_reduced_spec {
+    pub denominator: u32,
+    pub format: u32,
+    pub pitch: u32,
+}
+
 pub const COMPEG_OK: c_int = 0;
 pub const COMPEG_E_INVALID_ARG: c_int = -1;
 pub const COMPEG_E_UNSUPPORTED: c_int = -2;
@@ -149,6 +159,9 @@ pub const COMPEG_KERNEL_FUSED_LAYOUT: c_int = 6;
 pub const COMPEG_KERNEL_FUSED_STREAM: c_int = 7;
 pub const COMPEG_KERNEL_WALK_MCU: c_int = 8;
 pub const COMPEG_KERNEL_PLANES: c_int = 9;
+pub const COMPEG_KERNEL_REDUCED: c_int = 10;
+pub const COMPEG_REDUCED_RGBA: u32 = 0;
+pub const COMPEG_REDUCED_RGB_PLANAR: u32 = 1;
 pub const COMPEG_PLANES_PLANAR: u32 = 0;
 pub const COMPEG_PLANES_SEMIPLANAR: u32 = 1;
 pub const COMPEG_PLANES_YUYV: u32 = 2;
@@ -367,4 +380,12 @@ extern "C" {
                                         device_dst: *mut c_void, dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
     pub fn compeg_decoder_decode_planes_blocking(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_planes_spec,
                                                  device_dst: *mut c_void, dst_bytes: usize) -> c_int;
+    pub fn compeg_reduced_shape(spec: *const compeg_reduced_spec, width: u32, height: u32, out_width: *mut u32, out_height: *mut u32,
+                                pitch: *mut u32, total_bytes: *mut u64) -> c_int;
+    pub fn compeg_batch_decode_reduced(batch: *mut compeg_batch, spec: *const compeg_reduced_spec, device_dst: *mut c_void,
+                                       dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_decoder_decode_reduced(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_reduced_spec,
+                                         device_dst: *mut c_void, dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_decoder_decode_reduced_blocking(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_reduced_spec,
+                                                  device_dst: *mut c_void, dst_bytes: usize) -> c_int;
 }

@@ -384,6 +384,53 @@ pub fn planes_shape(spec: &PlanesSpec, width: u32, height: u32, components: u32,
     Ok(layout)
 }
 
+/// The format of a reduced decode (compeg_hip.h, "Reduced-size decode").
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum ReducedFormat {
+    /// Interleaved R G B A, A = 255; address and pitch multiples of 4.
+    Rgba,
+    /// `[3, oh, ow]` bytes, tight: a CHW u8 tensor.
+    RgbPlanar,
+}
+
+/// What `Decoder::decode_reduced` / `Batch::decode_reduced` write: the image at 1/8 scale, one RGB pixel per luma data
+/// unit from the DC terms alone.  `pitch`: the RGBA rows' pitch in bytes, 0 = tight.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct ReducedSpec {
+    pub format: ReducedFormat,
+    pub pitch: u32,
+}
+
+/// `reduced_shape`'s answer: the reduced extent, the pitch in use and one image's bytes.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct ReducedShape {
+    pub width: u32,
+    pub height: u32,
+    pub pitch: u32,
+    pub total_bytes: u64,
+}
+
+impl ReducedSpec {
+    pub fn new(format: ReducedFormat) -> Self {
+        ReducedSpec { format, pitch: 0 }
+    }
+
+    fn raw(&self) -> ffi::compeg_reduced_spec {
+        let format = match self.format {
+            ReducedFormat::Rgba => ffi::COMPEG_REDUCED_RGBA,
+            ReducedFormat::RgbPlanar => ffi::COMPEG_REDUCED_RGB_PLANAR,
+        };
+        ffi::compeg_reduced_spec { denominator: 8, format, pitch: self.pitch }
+    }
+}
+
+/// No device needed: the 1/8-scale extent and size of a `width x height` image.
+pub fn reduced_shape(spec: &ReducedSpec, width: u32, height: u32) -> Result<ReducedShape> {
+    let mut s = ReducedShape { width: 0, height: 0, pitch: 0, total_bytes: 0 };
+    check(unsafe { ffi::compeg_reduced_shape(&spec.raw(), width, height, &mut s.width, &mut s.height, &mut s.pitch, &mut s.total_bytes) })?;
+    Ok(s)
+}
+
 /// The weights of `Decoder::pack_tensor_luma` / `Batch::pack_tensor_luma` (compeg_hip.h, "Luma tensor output"): per source
 /// pixel `L = (wR R + wG G + wB B + 32768) >> 16`; the destination is `[count][1][oh][ow]`.  A grayscale frame gives its
 /// own values under any of them.
@@ -782,6 +829,26 @@ impl Decoder {
         check(ffi::compeg_decoder_decode_planes_blocking(self.raw.as_ptr(), image.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes))
     }
 
+    /// Extension: uploads and preprocesses `image` as `enqueue` does and records, on `stream`, a decode at 1/8 scale
+    /// into caller-owned device memory as `reduced_shape` lays it out.  The texture and what the packs read are not
+    /// touched.  Returns without waiting: synchronise `stream`, or use `decode_reduced_blocking`.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn decode_reduced(&mut self, image: &ImageData, spec: &ReducedSpec, device_dst: *mut c_void, dst_bytes: usize,
+                                 stream: Stream) -> Result<()> {
+        check(ffi::compeg_decoder_decode_reduced(self.raw.as_ptr(), image.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
+    }
+
+    /// `decode_reduced` on the gpu's own stream, and the wait for it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes.
+    pub unsafe fn decode_reduced_blocking(&mut self, image: &ImageData, spec: &ReducedSpec, device_dst: *mut c_void,
+                                          dst_bytes: usize) -> Result<()> {
+        check(ffi::compeg_decoder_decode_reduced_blocking(self.raw.as_ptr(), image.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes))
+    }
+
     /// Test helper (the reference's tests copy the texture to a buffer): waits and
     /// returns the image's `width x height` corner, tightly packed.
     pub fn read_output(&mut self, width: u32, height: u32) -> Result<Vec<u8>> {
@@ -1031,6 +1098,16 @@ impl Batch {
     /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
     pub unsafe fn decode_planes(&mut self, spec: &PlanesSpec, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
         check(ffi::compeg_batch_decode_planes(self.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
+    }
+
+    /// Extension: records a decode of the last upload's images (all of one size and sampling) at 1/8 scale into
+    /// caller-owned device memory, image i at `i * total_bytes` of `reduced_shape`.  The RGBA outputs are not touched.
+    /// Returns without waiting; `wait` covers it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn decode_reduced(&mut self, spec: &ReducedSpec, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        check(ffi::compeg_batch_decode_reduced(self.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
     }
 
     /// The EXIF orientation tag (1..8) of image `index` of the last upload.
