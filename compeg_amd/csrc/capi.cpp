@@ -1800,6 +1800,99 @@ const char *sampling_name(uint32_t components, uint32_t hs, uint32_t vs)
     return hs == 2 && vs == 1 ? "4:2:2" : hs == 1 && vs == 1 ? "4:4:4" : hs == 1 && vs == 2 ? "4:4:0" : hs == 2 && vs == 2 ? "4:2:0" : "unknown";
 }
 
+// Decodes into the caller's memory (planes, reduced), every entry point of every output down one road (decode_to_caller).
+// What such a decode is laid out for: a decoder's image, or the one size and sampling all images of a batch share.
+struct DecodeFacts {
+    uint32_t width, height, components, hs, vs; // (hs x vs: the file's luma sampling factors)
+    size_t images;
+};
+
+// ... of the decoder's image: 0 with *f filled in, or the error recorded
+int decode_facts(compeg_decoder *dec, const compeg_image *img, const char *, const void *, DecodeFacts *f)
+{
+    if (!dec || !img)
+        return fail(COMPEG_E_INVALID_ARG, "NULL argument");
+    const ImageData &data = *img->data;
+    *f = DecodeFacts{data.width, data.height, data.components, data.metadata.components[0].hsample, data.metadata.components[0].vsample, 1};
+    return COMPEG_OK;
+}
+
+// ... of the batch's finished upload, whose images must be of one size and one sampling (prefix: the output's name)
+int decode_facts(compeg_batch *batch, const compeg_image *, const char *prefix, const void *spec, DecodeFacts *f)
+{
+    if (!batch)
+        return fail(COMPEG_E_INVALID_ARG, null_text(batch));
+    if (!spec)
+        return fail(COMPEG_E_INVALID_ARG, "spec is NULL");
+    const Status s = batch->finish_upload(); // (the descriptors looked at below are the finished upload's)
+    if (!s.ok())
+        return fail(s);
+    const std::string name = prefix;
+    if (batch->count == 0)
+        return fail(COMPEG_E_INVALID_ARG, (name + ": nothing uploaded yet").c_str());
+    const ImageDesc &first = batch->descs[0];
+    const uint32_t comps0 = first.dus_per_mcu == 1 ? 1u : 3u;
+    for (size_t i = 1; i < batch->count; i++) {
+        const ImageDesc &d = batch->descs[i];
+        if (d.out_w != first.out_w || d.out_h != first.out_h)
+            return fail(COMPEG_E_INVALID_ARG, (name + ": the batch's images are not all of one size (image " + std::to_string(i) + " is " +
+                                               std::to_string(d.out_w) + "x" + std::to_string(d.out_h) + ", image 0 " + std::to_string(first.out_w) + "x" +
+                                               std::to_string(first.out_h) + ")").c_str());
+        const uint32_t comps = d.dus_per_mcu == 1 ? 1u : 3u;
+        if (comps != comps0 || d.hsample[0] != first.hsample[0] || d.vsample[0] != first.vsample[0])
+            return fail(COMPEG_E_INVALID_ARG, (name + ": the batch's images are not all of one sampling (image " + std::to_string(i) + " is " +
+                                               sampling_name(comps, d.hsample[0], d.vsample[0]) + ", image 0 " +
+                                               sampling_name(comps0, first.hsample[0], first.vsample[0]) + ")").c_str());
+    }
+    *f = DecodeFacts{first.out_w, first.out_h, comps0, first.hsample[0], first.vsample[0], batch->count};
+    return COMPEG_OK;
+}
+
+// The destination holds `images` images of `total` bytes.
+int check_destination(const char *prefix, const void *device_dst, size_t dst_bytes, uint64_t total, size_t images)
+{
+    if (!device_dst)
+        return fail(COMPEG_E_INVALID_ARG, "device_dst is NULL");
+    if (uint64_t(dst_bytes) / total < images)
+        return fail(COMPEG_E_INVALID_ARG, (std::string(prefix) + ": dst_bytes is " + std::to_string(dst_bytes) + ", " + std::to_string(images) +
+                                           " image(s) of " + std::to_string(total) + " bytes need " + std::to_string(total * images)).c_str());
+    return COMPEG_OK;
+}
+
+// (luma sampling as the kernels take it: 1 x 0 for a grayscale image)
+Status decode_into(compeg_decoder &dec, const compeg_image *img, const CallerDecode &into, const DecodeFacts &, hipStream_t stream)
+{
+    return dec.enqueue(*img->data, stream, nullptr, false, &into);
+}
+Status decode_into(compeg_batch &batch, const compeg_image *, const CallerDecode &into, const DecodeFacts &f, hipStream_t stream)
+{
+    return batch.decode_into(into, f.hs, f.components == 1 ? 0u : f.vs, stream);
+}
+
+// Output: the spec with what is its own -- the target laid out for the facts and the destination checked against it
+// (target_for: 0, or the error recorded), and the runtime's description of the decode.  img: the decoder's.
+// blocking: (decoders, hip_stream NULL: the gpu's own stream) the call waits for the stream.
+template <class Owner, class Output>
+int decode_to_caller(Owner *owner, const compeg_image *img, const Output &output, void *device_dst, size_t dst_bytes, void *hip_stream,
+                     bool blocking = false)
+{
+    return guarded([&] {
+        DecodeFacts facts;
+        typename Output::Target target;
+        int rc = decode_facts(owner, img, Output::kPrefix, output.spec, &facts);
+        if (rc == COMPEG_OK)
+            rc = output.target_for(facts, device_dst, dst_bytes, &target);
+        if (rc != COMPEG_OK)
+            return rc;
+        const hipStream_t stream = stream_of(*owner, hip_stream);
+        const Status s = decode_into(*owner, img, Output::decode(target), facts, stream);
+        if (!s.ok())
+            return fail(s);
+        const hipError_t e = blocking ? hipStreamSynchronize(stream) : hipSuccess;
+        return e == hipSuccess ? ok() : fail(hip_status(e, "hipStreamSynchronize"));
+    });
+}
+
 // compeg_planes_spec as the header has it, laid out for a width x height image: 0 with *out filled in, or the error
 // recorded.  (The texts name values, not the header's macros.)
 int planes_layout(const compeg_planes_spec *spec, uint32_t width, uint32_t height, uint32_t components, uint32_t hs, uint32_t vs,
@@ -1884,30 +1977,22 @@ PlanesTarget planes_target(const compeg_planes_spec &spec, const compeg_planes_l
     return t;
 }
 
-int check_planes_destination(const void *device_dst, size_t dst_bytes, uint64_t total, size_t images)
-{
-    if (!device_dst)
-        return fail(COMPEG_E_INVALID_ARG, "device_dst is NULL");
-    if (uint64_t(dst_bytes) / total < images)
-        return fail(COMPEG_E_INVALID_ARG, ("planes: dst_bytes is " + std::to_string(dst_bytes) + ", " + std::to_string(images) + " image(s) of " +
-                                           std::to_string(total) + " bytes need " + std::to_string(total * images)).c_str());
-    return COMPEG_OK;
-}
-
-int decoder_planes(compeg_decoder *dec, const compeg_image *img, const compeg_planes_spec *spec, void *device_dst, size_t dst_bytes,
-                   hipStream_t stream)
-{
-    const ImageData &data = *img->data;
-    compeg_planes_layout l;
-    int rc = planes_layout(spec, data.width, data.height, data.components, data.metadata.components[0].hsample, data.metadata.components[0].vsample, &l);
-    if (rc == COMPEG_OK)
-        rc = check_planes_destination(device_dst, dst_bytes, l.total_bytes, 1);
-    if (rc != COMPEG_OK)
+struct PlanesOutput {
+    using Target = PlanesTarget;
+    static constexpr const char *kPrefix = "planes";
+    const compeg_planes_spec *spec;
+    int target_for(const DecodeFacts &f, void *device_dst, size_t dst_bytes, PlanesTarget *target) const
+    {
+        compeg_planes_layout l;
+        int rc = planes_layout(spec, f.width, f.height, f.components, f.hs, f.vs, &l);
+        if (rc == COMPEG_OK)
+            rc = check_destination(kPrefix, device_dst, dst_bytes, l.total_bytes, f.images);
+        if (rc == COMPEG_OK)
+            *target = planes_target(*spec, l, device_dst);
         return rc;
-    const PlanesTarget target = planes_target(*spec, l, device_dst);
-    Status s = dec->enqueue(data, stream, nullptr, false, &target);
-    return s.ok() ? ok() : fail(s);
-}
+    }
+    static CallerDecode decode(const PlanesTarget &target) { return planes_decode(target); }
+};
 
 } // namespace
 
@@ -1935,64 +2020,19 @@ int compeg_planes_shape(const compeg_planes_spec *spec, uint32_t width, uint32_t
 
 int compeg_batch_decode_planes(compeg_batch *batch, const compeg_planes_spec *spec, void *device_dst, size_t dst_bytes, void *hip_stream)
 {
-    return guarded([&] {
-        if (!batch)
-            return fail(COMPEG_E_INVALID_ARG, null_text(batch));
-        if (!spec)
-            return fail(COMPEG_E_INVALID_ARG, "spec is NULL");
-        Status s = batch->finish_upload(); // (the descriptors looked at below are the finished upload's)
-        if (!s.ok())
-            return fail(s);
-        if (batch->count == 0)
-            return fail(COMPEG_E_INVALID_ARG, "planes: nothing uploaded yet");
-        const ImageDesc &first = batch->descs[0];
-        const uint32_t comps0 = first.dus_per_mcu == 1 ? 1u : 3u;
-        for (size_t i = 1; i < batch->count; i++) {
-            const ImageDesc &d = batch->descs[i];
-            if (d.out_w != first.out_w || d.out_h != first.out_h)
-                return fail(COMPEG_E_INVALID_ARG, ("planes: the batch's images are not all of one size (image " + std::to_string(i) + " is " +
-                                                   std::to_string(d.out_w) + "x" + std::to_string(d.out_h) + ", image 0 " + std::to_string(first.out_w) + "x" +
-                                                   std::to_string(first.out_h) + ")").c_str());
-            const uint32_t comps = d.dus_per_mcu == 1 ? 1u : 3u;
-            if (comps != comps0 || d.hsample[0] != first.hsample[0] || d.vsample[0] != first.vsample[0])
-                return fail(COMPEG_E_INVALID_ARG, (std::string("planes: the batch's images are not all of one sampling (image ") + std::to_string(i) + " is " +
-                                                   sampling_name(comps, d.hsample[0], d.vsample[0]) + ", image 0 " +
-                                                   sampling_name(comps0, first.hsample[0], first.vsample[0]) + ")").c_str());
-        }
-        compeg_planes_layout l;
-        int rc = planes_layout(spec, first.out_w, first.out_h, comps0, first.hsample[0], first.vsample[0], &l);
-        if (rc == COMPEG_OK)
-            rc = check_planes_destination(device_dst, dst_bytes, l.total_bytes, batch->count);
-        if (rc != COMPEG_OK)
-            return rc;
-        s = batch->decode_planes(planes_target(*spec, l, device_dst), first.hsample[0], comps0 == 1 ? 0u : first.vsample[0],
-                                 stream_of(*batch, hip_stream));
-        return s.ok() ? ok() : fail(s);
-    });
+    return decode_to_caller(batch, nullptr, PlanesOutput{spec}, device_dst, dst_bytes, hip_stream);
 }
 
 int compeg_decoder_decode_planes(compeg_decoder *dec, const compeg_image *img, const compeg_planes_spec *spec, void *device_dst,
                                  size_t dst_bytes, void *hip_stream)
 {
-    return guarded([&] {
-        if (!dec || !img)
-            return fail(COMPEG_E_INVALID_ARG, "NULL argument");
-        return decoder_planes(dec, img, spec, device_dst, dst_bytes, stream_of(*dec, hip_stream));
-    });
+    return decode_to_caller(dec, img, PlanesOutput{spec}, device_dst, dst_bytes, hip_stream);
 }
 
 int compeg_decoder_decode_planes_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_planes_spec *spec, void *device_dst,
                                           size_t dst_bytes)
 {
-    return guarded([&] {
-        if (!dec || !img)
-            return fail(COMPEG_E_INVALID_ARG, "NULL argument");
-        const int rc = decoder_planes(dec, img, spec, device_dst, dst_bytes, dec->gpu->stream);
-        if (rc != COMPEG_OK)
-            return rc;
-        const hipError_t e = hipStreamSynchronize(dec->gpu->stream);
-        return e == hipSuccess ? ok() : fail(hip_status(e, "hipStreamSynchronize"));
-    });
+    return decode_to_caller(dec, img, PlanesOutput{spec}, device_dst, dst_bytes, nullptr, true);
 }
 
 } // extern "C"
@@ -2039,18 +2079,6 @@ int reduced_layout(const compeg_reduced_spec *spec, uint32_t width, uint32_t hei
     return COMPEG_OK;
 }
 
-int check_reduced_destination(const compeg_reduced_spec &spec, const void *device_dst, size_t dst_bytes, uint64_t total, size_t images)
-{
-    if (!device_dst)
-        return fail(COMPEG_E_INVALID_ARG, "device_dst is NULL");
-    if (spec.format == COMPEG_REDUCED_RGBA && reinterpret_cast<uintptr_t>(device_dst) % 4u != 0u)
-        return fail(COMPEG_E_INVALID_ARG, "reduced: the rgba destination's address is not a multiple of 4");
-    if (uint64_t(dst_bytes) / total < images)
-        return fail(COMPEG_E_INVALID_ARG, ("reduced: dst_bytes is " + std::to_string(dst_bytes) + ", " + std::to_string(images) + " image(s) of " +
-                                           std::to_string(total) + " bytes need " + std::to_string(total * images)).c_str());
-    return COMPEG_OK;
-}
-
 ReducedTarget reduced_target(const compeg_reduced_spec &spec, const ReducedLayout &l, void *device_dst)
 {
     ReducedTarget t{};
@@ -2063,20 +2091,24 @@ ReducedTarget reduced_target(const compeg_reduced_spec &spec, const ReducedLayou
     return t;
 }
 
-int decoder_reduced(compeg_decoder *dec, const compeg_image *img, const compeg_reduced_spec *spec, void *device_dst, size_t dst_bytes,
-                    hipStream_t stream)
-{
-    const ImageData &data = *img->data;
-    ReducedLayout l;
-    int rc = reduced_layout(spec, data.width, data.height, &l);
-    if (rc == COMPEG_OK)
-        rc = check_reduced_destination(*spec, device_dst, dst_bytes, l.total, 1);
-    if (rc != COMPEG_OK)
+struct ReducedOutput {
+    using Target = ReducedTarget;
+    static constexpr const char *kPrefix = "reduced";
+    const compeg_reduced_spec *spec;
+    int target_for(const DecodeFacts &f, void *device_dst, size_t dst_bytes, ReducedTarget *target) const
+    {
+        ReducedLayout l;
+        int rc = reduced_layout(spec, f.width, f.height, &l);
+        if (rc == COMPEG_OK && spec->format == COMPEG_REDUCED_RGBA && reinterpret_cast<uintptr_t>(device_dst) % 4u != 0u)
+            rc = fail(COMPEG_E_INVALID_ARG, "reduced: the rgba destination's address is not a multiple of 4");
+        if (rc == COMPEG_OK)
+            rc = check_destination(kPrefix, device_dst, dst_bytes, l.total, f.images);
+        if (rc == COMPEG_OK)
+            *target = reduced_target(*spec, l, device_dst);
         return rc;
-    const ReducedTarget target = reduced_target(*spec, l, device_dst);
-    Status s = dec->enqueue(data, stream, nullptr, false, nullptr, &target);
-    return s.ok() ? ok() : fail(s);
-}
+    }
+    static CallerDecode decode(const ReducedTarget &target) { return reduced_decode(target); }
+};
 
 } // namespace
 
@@ -2104,64 +2136,19 @@ int compeg_reduced_shape(const compeg_reduced_spec *spec, uint32_t width, uint32
 
 int compeg_batch_decode_reduced(compeg_batch *batch, const compeg_reduced_spec *spec, void *device_dst, size_t dst_bytes, void *hip_stream)
 {
-    return guarded([&] {
-        if (!batch)
-            return fail(COMPEG_E_INVALID_ARG, null_text(batch));
-        if (!spec)
-            return fail(COMPEG_E_INVALID_ARG, "spec is NULL");
-        Status s = batch->finish_upload(); // (the descriptors looked at below are the finished upload's)
-        if (!s.ok())
-            return fail(s);
-        if (batch->count == 0)
-            return fail(COMPEG_E_INVALID_ARG, "reduced: nothing uploaded yet");
-        const ImageDesc &first = batch->descs[0];
-        const uint32_t comps0 = first.dus_per_mcu == 1 ? 1u : 3u;
-        for (size_t i = 1; i < batch->count; i++) {
-            const ImageDesc &d = batch->descs[i];
-            if (d.out_w != first.out_w || d.out_h != first.out_h)
-                return fail(COMPEG_E_INVALID_ARG, ("reduced: the batch's images are not all of one size (image " + std::to_string(i) + " is " +
-                                                   std::to_string(d.out_w) + "x" + std::to_string(d.out_h) + ", image 0 " + std::to_string(first.out_w) + "x" +
-                                                   std::to_string(first.out_h) + ")").c_str());
-            const uint32_t comps = d.dus_per_mcu == 1 ? 1u : 3u;
-            if (comps != comps0 || d.hsample[0] != first.hsample[0] || d.vsample[0] != first.vsample[0])
-                return fail(COMPEG_E_INVALID_ARG, (std::string("reduced: the batch's images are not all of one sampling (image ") + std::to_string(i) + " is " +
-                                                   sampling_name(comps, d.hsample[0], d.vsample[0]) + ", image 0 " +
-                                                   sampling_name(comps0, first.hsample[0], first.vsample[0]) + ")").c_str());
-        }
-        ReducedLayout l;
-        int rc = reduced_layout(spec, first.out_w, first.out_h, &l);
-        if (rc == COMPEG_OK)
-            rc = check_reduced_destination(*spec, device_dst, dst_bytes, l.total, batch->count);
-        if (rc != COMPEG_OK)
-            return rc;
-        s = batch->decode_reduced(reduced_target(*spec, l, device_dst), first.hsample[0], comps0 == 1 ? 0u : first.vsample[0],
-                                  stream_of(*batch, hip_stream));
-        return s.ok() ? ok() : fail(s);
-    });
+    return decode_to_caller(batch, nullptr, ReducedOutput{spec}, device_dst, dst_bytes, hip_stream);
 }
 
 int compeg_decoder_decode_reduced(compeg_decoder *dec, const compeg_image *img, const compeg_reduced_spec *spec, void *device_dst,
                                   size_t dst_bytes, void *hip_stream)
 {
-    return guarded([&] {
-        if (!dec || !img)
-            return fail(COMPEG_E_INVALID_ARG, "NULL argument");
-        return decoder_reduced(dec, img, spec, device_dst, dst_bytes, stream_of(*dec, hip_stream));
-    });
+    return decode_to_caller(dec, img, ReducedOutput{spec}, device_dst, dst_bytes, hip_stream);
 }
 
 int compeg_decoder_decode_reduced_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_reduced_spec *spec, void *device_dst,
                                            size_t dst_bytes)
 {
-    return guarded([&] {
-        if (!dec || !img)
-            return fail(COMPEG_E_INVALID_ARG, "NULL argument");
-        const int rc = decoder_reduced(dec, img, spec, device_dst, dst_bytes, dec->gpu->stream);
-        if (rc != COMPEG_OK)
-            return rc;
-        const hipError_t e = hipStreamSynchronize(dec->gpu->stream);
-        return e == hipSuccess ? ok() : fail(hip_status(e, "hipStreamSynchronize"));
-    });
+    return decode_to_caller(dec, img, ReducedOutput{spec}, device_dst, dst_bytes, nullptr, true);
 }
 
 } // extern "C"

@@ -103,9 +103,7 @@ CG_DEV void gray_init(GrayPixels<MC> &t, const ImageDesc &d, uint32_t interval, 
 #pragma unroll
         for (int w = 0; w < 16; w++)
             t.px[k][w] = 0u;
-    const uint32_t mcu0 = interval * d.restart_interval;
-    t.mx = mcu0 % d.width_mcus;
-    t.my = mcu0 / d.width_mcus;
+    mcu_cursor_init(t, d, interval);
     t.active = active;
 }
 

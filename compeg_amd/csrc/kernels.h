@@ -13,6 +13,13 @@
 
 namespace compeg {
 
+// The compute units and the LDS per compute unit of the device the calling thread has current, asked once per device
+// (kernels.hip): what the planners size workgroups and grids for and the launches raise their kernels' LDS limit to.
+struct DeviceLimits {
+    uint32_t cus, lds_bytes;
+};
+DeviceLimits device_limits();
+
 // Chooses workgroup shape and LDS carve-up for a decode of `images` images
 // whose largest image has `max_intervals` restart intervals and `max_l2`
 // L2 entries; max_wave_words (largest scan span of 64 consecutive intervals)
@@ -210,6 +217,37 @@ hipError_t launch_planes(const ImageDesc *descs, uint32_t images, uint32_t max_i
 uint32_t reduced_wave_cap();
 hipError_t launch_reduced(const ImageDesc *descs, uint32_t images, uint32_t max_intervals, const HuffLdsPlan &plan, uint32_t hs, uint32_t vs,
                           const ReducedTarget &target, hipStream_t stream);
+
+// A decode into the caller's memory, as the runtime's one road for them takes it (compeg_decoder::enqueue,
+// compeg_batch::decode_into): how to plan it, how to launch it, what to record.  A further output of this shape is a
+// further maker below, nothing in the runtime.
+struct CallerDecode {
+    const void *target; // the family's target (the maker's argument: it outlives the call), validated by the caller
+    // images first .. first + images - 1 of the target, their descriptors from descs on
+    hipError_t (*launch)(const void *target, uint32_t first, const ImageDesc *descs, uint32_t images, uint32_t max_intervals,
+                         const HuffLdsPlan &plan, uint32_t hs, uint32_t vs, hipStream_t stream);
+    bool fused;                                     // plan_huffman's flag ...
+    uint32_t (*wave_cap)(uint32_t hs, uint32_t vs); // ... and its wave_cap
+    int kernel_id;                                  // COMPEG_KERNEL_*
+};
+template <class Target, hipError_t (*Launch)(const ImageDesc *, uint32_t, uint32_t, const HuffLdsPlan &, uint32_t, uint32_t, const Target &, hipStream_t)>
+hipError_t launch_caller_decode(const void *target, uint32_t first, const ImageDesc *descs, uint32_t images, uint32_t max_intervals,
+                                const HuffLdsPlan &plan, uint32_t hs, uint32_t vs, hipStream_t stream)
+{
+    Target part = *static_cast<const Target *>(target);
+    part.dst += uint64_t(first) * part.image_stride;
+    return Launch(descs, images, max_intervals, plan, hs, vs, part, stream);
+}
+inline CallerDecode planes_decode(const PlanesTarget &target)
+{
+    return CallerDecode{&target, launch_caller_decode<PlanesTarget, launch_planes>, true, planes_wave_cap, COMPEG_KERNEL_PLANES};
+}
+// (fused = false: the entropy walk's occupancy)
+inline CallerDecode reduced_decode(const ReducedTarget &target)
+{
+    return CallerDecode{&target, launch_caller_decode<ReducedTarget, launch_reduced>, false,
+                        [](uint32_t, uint32_t) { return reduced_wave_cap(); }, COMPEG_KERNEL_REDUCED};
+}
 
 #if defined(CG_AC_STAMPS)
 // diagnostic build: AC-loop cycle counters (kernels_body.h)

@@ -27,7 +27,7 @@
 #include "gray_body.h"
 #include "coop_body.h"
 #include "walk_body.h"
-#include "kernels.h"
+#include "whole_window.h"
 #include "lab.h"
 
 namespace compeg {
@@ -36,10 +36,7 @@ namespace compeg {
 // calling thread has current (256 and 160 KB on an MI355X in its default mode; fewer CUs in a partitioned mode), asked
 // once per device.  (A failed query -- nothing else would work either -- leaves the figures of the one architecture
 // the library opens a device of: compeg_gpu_open refuses anything but gfx950.)
-struct DeviceLimits {
-    uint32_t cus, lds_bytes;
-};
-static DeviceLimits device_limits()
+DeviceLimits device_limits()
 {
     static std::atomic<uint64_t> known[64]; // cus << 32 | lds_bytes
     int dev = 0;
@@ -376,44 +373,19 @@ decode_fused_422_mcu_rec_kernel(const ImageDesc *__restrict__ descs, uint32_t l2
 {
     fused_kernel_body<Wave422<true, true>, kMcuQueueGroup>(descs, l2_in_lds, window_words, waves_per_image, images, queue);
 }
-// Extension layouts: decode_wave_fused_layout behind the plain prologue -- grid (workgroups per image,
-// images), no resident waves: inside the larger body above these kernels spill (4:2:0: 356 registers), alone they
+// Extension layouts: decode_wave_fused_layout behind the plain prologue (whole_window.h) -- grid
+// (workgroups per image, images), no resident waves: inside the larger body above these kernels spill (4:2:0: 356 registers), alone they
 // do not (134 / 152 / 186 VGPRs).  Luma 1x1 (4:4:4), 1x2 (4:4:0) ...
 // (VS = 0: no chroma -- a grayscale image's one data unit an MCU, decode_wave_fused_gray)
 template <int HS, int VS, int MC>
 __device__ __forceinline__ void fused_layout_kernel_body(const ImageDesc *__restrict__ descs, uint32_t l2_in_lds, uint32_t window_words)
 {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const ImageDesc &d = descs[blockIdx.y];
-    const uint32_t first_interval = blockIdx.x * blockDim.x;
-    if (first_interval >= d.total_intervals)
-        return;
-    uint16_t *l1 = reinterpret_cast<uint16_t *>(smem);
-    uint16_t *l2 = l1 + kL1Entries;
-    const uint32_t wave_area = align16(window_words * 4u) + kWave * kDuSlotBytes;
-    uint8_t *wave_base = smem + align16((kL1Entries + l2_in_lds) * 2u);
-    const uint32_t wave = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x / kWave))), lane = threadIdx.x % kWave;
-    uint32_t *win = reinterpret_cast<uint32_t *>(wave_base + wave * wave_area);
-    const uint32_t wave_first = first_interval + wave * kWave;
-    uint32_t win_base = 0, win_len = 0;
-    if (wave_first < d.total_intervals)
-        wave_window(d, wave_first, window_words, win_base, win_len);
-    stage_luts_and_window(d, l1, l2, l2_in_lds, threadIdx.x, blockDim.x, win, win_base, win_len, lane);
-    __syncthreads();
-    if (wave_first >= d.total_intervals)
-        return; // the whole wave; lanes past the last interval of a partly used wave stay (quad exchange)
-    HuffShared s;
-    s.l1 = l1;
-    s.l2 = l2;
-    s.l2_staged = umin(l2_in_lds, d.fast_off + 2u * kFastEntries);
-    s.win = win;
-    s.win_base = win_base;
-    s.win_len = win_len;
-    s.du_slots = reinterpret_cast<uint8_t *>(win) + align16(window_words * 4u);
-    if constexpr (VS == 0)
-        decode_wave_fused_gray<MC>(d, s, wave_first + lane, lane);
-    else
-        decode_wave_fused_layout<HS, VS, MC>(d, s, wave_first + lane, lane);
+    whole_window_kernel(descs, l2_in_lds, window_words, [](const ImageDesc &d, const HuffShared &s, uint32_t interval, uint32_t lane) {
+        if constexpr (VS == 0)
+            decode_wave_fused_gray<MC>(d, s, interval, lane);
+        else
+            decode_wave_fused_layout<HS, VS, MC>(d, s, interval, lane);
+    });
 }
 
 // (4:4:4 and 4:4:0: MCUs in pairs -- rows of 64 bytes; the last MCU of an odd restart interval alone -- from two MCUs an interval on: two waves to a SIMD;
@@ -882,58 +854,29 @@ HuffLdsPlan plan_huffman(uint32_t max_intervals, uint32_t images, uint32_t max_l
 hipError_t launch_huffman(const ImageDesc *descs, uint32_t images, uint32_t max_intervals,
                           const HuffLdsPlan &plan, hipStream_t stream)
 {
-    if (images == 0 || max_intervals == 0)
-        return hipSuccess;
-    const uint32_t threads = plan.waves_per_block * kWave;
-    dim3 grid((max_intervals + threads - 1) / threads, images, 1);
-    const hipError_t attr = hipFuncSetAttribute(
-        reinterpret_cast<const void *>(huffman_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-        int(device_limits().lds_bytes));
-    if (attr != hipSuccess)
-        return attr;
-    hipLaunchKernelGGL(huffman_kernel, grid, dim3(threads), plan.total_bytes, stream, descs,
-                       plan.l2_entries_in_lds, plan.window_words);
-    return hipGetLastError();
+    return launch_interval_grid(huffman_kernel, descs, images, max_intervals, plan, stream);
 }
 
 hipError_t launch_entropy(const ImageDesc *descs, uint32_t images, uint32_t max_intervals,
                           const HuffLdsPlan &plan, hipStream_t stream)
 {
-    if (images == 0 || max_intervals == 0)
-        return hipSuccess;
-    const uint32_t threads = plan.waves_per_block * kWave;
-    dim3 grid((max_intervals + threads - 1) / threads, images, 1);
-    const hipError_t attr = hipFuncSetAttribute(
-        reinterpret_cast<const void *>(entropy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-        int(device_limits().lds_bytes));
-    if (attr != hipSuccess)
-        return attr;
-    hipLaunchKernelGGL(entropy_kernel, grid, dim3(threads), plan.total_bytes, stream, descs,
-                       plan.l2_entries_in_lds, plan.window_words);
-    return hipGetLastError();
+    return launch_interval_grid(entropy_kernel, descs, images, max_intervals, plan, stream);
 }
 
 hipError_t launch_fused_layout(const ImageDesc *descs, uint32_t images, uint32_t max_intervals, const HuffLdsPlan &plan,
                                uint32_t hs, uint32_t vs, bool pairs, hipStream_t stream)
 {
-    if (images == 0 || max_intervals == 0)
-        return hipSuccess;
     using Kernel = void (*)(const ImageDesc *, uint32_t, uint32_t);
-    const Kernel kernel = hs == 1 && vs == 1   ? (pairs ? decode_fused_444_kernel : decode_fused_444_single_kernel)
-                          : hs == 1 && vs == 2 ? (pairs ? decode_fused_440_kernel : decode_fused_440_single_kernel)
-                          : hs == 2 && vs == 2 ? decode_fused_420_kernel
-                          : hs == 1 && vs == 0 ? (pairs ? decode_fused_gray_kernel : decode_fused_gray_single_kernel)
-                                               : nullptr;
+    static constexpr Kernel kKernels[kSamplings][2] = {{nullptr, nullptr}, // (4:2:2: launch_fused_422)
+                                                       {decode_fused_444_single_kernel, decode_fused_444_kernel},
+                                                       {decode_fused_440_single_kernel, decode_fused_440_kernel},
+                                                       {decode_fused_420_kernel, decode_fused_420_kernel},
+                                                       {decode_fused_gray_single_kernel, decode_fused_gray_kernel}};
+    const uint32_t sampling = sampling_index(hs, vs);
+    const Kernel kernel = sampling == kSamplings ? nullptr : kKernels[sampling][pairs];
     if (!kernel || plan.waves_per_block > fused_layout_wave_cap(hs, vs, pairs))
         return hipErrorInvalidValue;
-    const uint32_t threads = plan.waves_per_block * kWave;
-    dim3 grid((max_intervals + threads - 1) / threads, images, 1);
-    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                int(device_limits().lds_bytes));
-    if (attr != hipSuccess)
-        return attr;
-    hipLaunchKernelGGL(kernel, grid, dim3(threads), plan.total_bytes, stream, descs, plan.l2_entries_in_lds, plan.window_words);
-    return hipGetLastError();
+    return launch_interval_grid(kernel, descs, images, max_intervals, plan, stream);
 }
 
 hipError_t launch_fused_422(const ImageDesc *descs, uint32_t images, uint32_t max_intervals,
@@ -1572,18 +1515,7 @@ hipError_t launch_idct_composite(const ImageDesc *descs, uint32_t images, uint32
 hipError_t launch_entropy_samples(const ImageDesc *descs, uint32_t images, uint32_t max_intervals,
                                   const HuffLdsPlan &plan, hipStream_t stream)
 {
-    if (images == 0 || max_intervals == 0)
-        return hipSuccess;
-    const uint32_t threads = plan.waves_per_block * kWave; // planned like the fused kernel: at most 12 waves
-    dim3 grid((max_intervals + threads - 1) / threads, images, 1);
-    const hipError_t attr = hipFuncSetAttribute(
-        reinterpret_cast<const void *>(entropy_samples_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-        int(device_limits().lds_bytes));
-    if (attr != hipSuccess)
-        return attr;
-    hipLaunchKernelGGL(entropy_samples_kernel, grid, dim3(threads), plan.total_bytes, stream, descs,
-                       plan.l2_entries_in_lds, plan.window_words);
-    return hipGetLastError();
+    return launch_interval_grid(entropy_samples_kernel, descs, images, max_intervals, plan, stream); // planned like the fused kernel: at most 12 waves
 }
 
 hipError_t launch_generic_composite(const ImageDesc *descs, uint32_t images, uint32_t max_w, uint32_t max_h,

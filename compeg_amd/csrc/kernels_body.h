@@ -1731,6 +1731,26 @@ CG_DEV void composite_generic_4px(const ImageDesc &d, uint32_t x0, uint32_t y, c
         q[3] = o.w;
 }
 
+// Where a lane's MCU lies in its image, in MCUs: the mx, my of every lane body's state of samples (C: PixelState,
+// LayoutPixels, GrayPixels, PlanesMcu, ReducedMcu).  The first MCU of restart interval `interval` ...
+template <class C>
+CG_DEV void mcu_cursor_init(C &c, const ImageDesc &d, uint32_t interval)
+{
+    const uint32_t mcu0 = interval * d.restart_interval;
+    c.mx = mcu0 % d.width_mcus;
+    c.my = mcu0 / d.width_mcus;
+}
+
+// ... and the one behind it in raster order.
+template <class C>
+CG_DEV void mcu_cursor_next(C &c, const ImageDesc &d)
+{
+    if (++c.mx >= d.width_mcus) {
+        c.mx = 0u;
+        c.my++;
+    }
+}
+
 // Transformer role: the samples of the MCU being assembled and where it goes.
 struct PixelState {
     uint32_t px[4][16]; // the MCU's four data units (Y0 Y1 Cb Cr), 4 samples per word
@@ -1745,9 +1765,7 @@ CG_DEV void pixel_init(PixelState &t, const ImageDesc &d, uint32_t interval, boo
 #pragma unroll
         for (int w = 0; w < 16; w++)
             t.px[k][w] = 0u;
-    const uint32_t mcu = interval * d.restart_interval;
-    t.mx = mcu % d.width_mcus;
-    t.my = mcu / d.width_mcus;
+    mcu_cursor_init(t, d, interval);
     t.active = active;
 }
 
@@ -1841,6 +1859,7 @@ CG_DEV McuTarget mcu_target(const PixelState &t, const ImageDesc &d)
     return g;
 }
 
+// (the 4:2:2 bodies' step, an equality: mcu_cursor_next's comparison is another instruction in their kernels)
 CG_DEV void pixel_next_mcu(PixelState &t, const ImageDesc &d)
 {
     t.mx++;
@@ -2484,9 +2503,7 @@ CG_DEV void layout_init(LayoutPixels<HS, VS, MC> &t, const ImageDesc &d, uint32_
 #pragma unroll
         for (int w = 0; w < 16; w++)
             t.px[k][w] = 0u;
-    const uint32_t mcu0 = interval * d.restart_interval;
-    t.mx = mcu0 % d.width_mcus;
-    t.my = mcu0 / d.width_mcus;
+    mcu_cursor_init(t, d, interval);
     t.active = active;
 }
 

@@ -213,9 +213,7 @@ CG_DEV void planes_init(PlanesMcu<HS, VS> &t, const ImageDesc &d, const PlanesTa
 #pragma unroll
         for (int w = 0; w < 16; w++)
             t.px[k][w] = 0u;
-    const uint32_t mcu0 = interval * d.restart_interval;
-    t.mx = mcu0 % d.width_mcus;
-    t.my = mcu0 / d.width_mcus;
+    mcu_cursor_init(t, d, interval);
     t.active = active;
     t.aligned = planes_aligned<HS, VS>(g, img);
 }
@@ -240,13 +238,11 @@ CG_DEV void planes_transform(PlanesMcu<HS, VS> &t, const ImageDesc &d, uint32_t 
     }
 }
 
+// (the name the wave function and the emulation driver step by)
 template <int HS, int VS>
 CG_DEV void planes_next_mcu(PlanesMcu<HS, VS> &t, const ImageDesc &d)
 {
-    if (++t.mx >= d.width_mcus) {
-        t.mx = 0u;
-        t.my++;
-    }
+    mcu_cursor_next(t, d);
 }
 
 #if defined(__HIPCC__)

@@ -44,9 +44,7 @@ CG_DEV void reduced_init(ReducedMcu<HS, VS> &t, const ImageDesc &d, uint32_t int
 {
     t.y = 0u;
     t.cb = t.cr = 128u;
-    const uint32_t mcu0 = interval * d.restart_interval;
-    t.mx = mcu0 % d.width_mcus;
-    t.my = mcu0 / d.width_mcus;
+    mcu_cursor_init(t, d, interval);
     t.active = active;
 }
 
@@ -116,13 +114,11 @@ CG_DEV void reduced_store_mcu(const ReducedMcu<HS, VS> &t, const ReducedTarget &
     }
 }
 
+// (the name the wave function and the emulation driver step by)
 template <int HS, int VS>
 CG_DEV void reduced_next_mcu(ReducedMcu<HS, VS> &t, const ImageDesc &d)
 {
-    if (++t.mx >= d.width_mcus) {
-        t.mx = 0u;
-        t.my++;
-    }
+    mcu_cursor_next(t, d);
 }
 
 #if defined(__HIPCC__)

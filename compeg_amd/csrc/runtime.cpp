@@ -615,10 +615,9 @@ Status compeg_decoder::finish_deferred(const ImageData &img, hipStream_t stream)
 }
 
 // Counterpart of Decoder::enqueue (src/lib.rs:385-477).
-Status compeg_decoder::enqueue(const ImageData &img, hipStream_t stream, bool *changed, bool may_defer, const PlanesTarget *planes,
-                               const ReducedTarget *reduced)
+Status compeg_decoder::enqueue(const ImageData &img, hipStream_t stream, bool *changed, bool may_defer, const CallerDecode *into)
 {
-    const bool caller_dst = planes || reduced; // a decode into the caller's memory, not the texture
+    const bool caller_dst = into != nullptr; // a decode into the caller's memory, not the texture
     EnqueueTrace trace;
     const auto t_enter = std::chrono::steady_clock::now();
     stage_times = compeg_stage_times{0.0, 0.0, 0.0};
@@ -876,21 +875,16 @@ Status compeg_decoder::enqueue(const ImageData &img, hipStream_t stream, bool *c
     const uint32_t luma_h = md.components[0].hsample, luma_v = layout_vs(img);
     // (8-pixel MCUs in pairs: rows of 64 bytes; of an odd interval the last MCU alone.  Intervals of one MCU: the single form)
     const bool mcu_pairs = luma_h == 1 && md.restart_interval >= 2u;
-    const HuffLdsPlan plan = reduced ? plan_huffman(md.total_restart_intervals, 1, staged_lut_entries(img), span, false, reduced_wave_cap())
-                                     : plan_huffman(md.total_restart_intervals, 1, staged_lut_entries(img), span, fused || !is_422(img) || planes,
-                                                    planes ? planes_wave_cap(luma_h, luma_v) : is_422(img) ? 0u : fused_layout_wave_cap(luma_h, luma_v, mcu_pairs));
+    const HuffLdsPlan plan = into ? plan_huffman(md.total_restart_intervals, 1, staged_lut_entries(img), span, into->fused, into->wave_cap(luma_h, luma_v))
+                                  : plan_huffman(md.total_restart_intervals, 1, staged_lut_entries(img), span, fused || !is_422(img),
+                                                 is_422(img) ? 0u : fused_layout_wave_cap(luma_h, luma_v, mcu_pairs));
     last_span = span;
     last_plan = plan;
     trace.mark("plan");
-    if (planes) {
-        // the planes decode: one kernel per sampling, a lane per restart interval, into the caller's memory
-        CG_HIP(launch_planes(reinterpret_cast<const ImageDesc *>(db), 1, md.total_restart_intervals, plan, luma_h, luma_v, *planes, stream));
-        last_kernel = COMPEG_KERNEL_PLANES;
-        coefficients_valid = false;
-    } else if (reduced) {
-        // the reduced decode: the same shape of launch, one pixel per luma data unit
-        CG_HIP(launch_reduced(reinterpret_cast<const ImageDesc *>(db), 1, md.total_restart_intervals, plan, luma_h, luma_v, *reduced, stream));
-        last_kernel = COMPEG_KERNEL_REDUCED;
+    if (into) {
+        // planes, reduced: one kernel per sampling, a lane per restart interval, into the caller's memory
+        CG_HIP(into->launch(into->target, 0, reinterpret_cast<const ImageDesc *>(db), 1, md.total_restart_intervals, plan, luma_h, luma_v, stream));
+        last_kernel = into->kernel_id;
         coefficients_valid = false;
     } else if (!is_422(img)) {
         // extension layouts (4:4:4, 4:4:0, 4:2:0): one fused kernel per layout (the development pipeline keeps the
@@ -2331,10 +2325,10 @@ Status compeg_batch::decode(hipStream_t stream)
     return Status{};
 }
 
-// Planes decode: the images of the last upload into the caller's memory.  It reads what decode() reads and writes
-// nothing of the batch's own but the units' scan results (mode 2), so it orders itself like a pack: behind the batch's
-// previous work on another stream, and the batch's next work on another stream behind it (note_pack: last_stream).
-Status compeg_batch::decode_planes(const PlanesTarget &target, uint32_t hs, uint32_t vs, hipStream_t stream)
+// A decode into the caller's memory (planes, reduced): the images of the last upload.  It reads what decode() reads and
+// writes nothing of the batch's own but the units' scan results (mode 2), so it orders itself like a pack: behind the
+// batch's previous work on another stream, and the batch's next work on another stream behind it (note_pack: last_stream).
+Status compeg_batch::decode_into(const CallerDecode &into, uint32_t hs, uint32_t vs, hipStream_t stream)
 {
     CG_TRY(finish_upload());
     if (count == 0)
@@ -2348,38 +2342,11 @@ Status compeg_batch::decode_planes(const PlanesTarget &target, uint32_t hs, uint
         CG_HIP(launch_scan(static_cast<const ScanDesc *>(scan_descs.ptr), n, max_tiles, stream));
     for (uint32_t at = 0; at < n; at += step) {
         const uint32_t m = std::min(step, n - at);
-        const HuffLdsPlan plan = plan_huffman(max_intervals, m, max_l2, max_span, true, planes_wave_cap(hs, vs));
-        PlanesTarget part = target;
-        part.dst = target.dst + uint64_t(at) * target.image_stride;
-        CG_HIP(launch_planes(dd + at, m, max_intervals, plan, hs, vs, part, stream));
+        const HuffLdsPlan plan = plan_huffman(max_intervals, m, max_l2, max_span, into.fused, into.wave_cap(hs, vs));
+        CG_HIP(into.launch(into.target, at, dd + at, m, max_intervals, plan, hs, vs, stream));
     }
-    last_kernel = COMPEG_KERNEL_PLANES;
+    last_kernel = into.kernel_id;
     decode_recorded = true; // (something of the batch's is on last_stream: what order_pack_behind_decode asks)
-    return note_pack(stream);
-}
-
-// Reduced decode: decode_planes' road with the 1/8-scale kernels at its end.
-Status compeg_batch::decode_reduced(const ReducedTarget &target, uint32_t hs, uint32_t vs, hipStream_t stream)
-{
-    CG_TRY(finish_upload());
-    if (count == 0)
-        return Status{};
-    CG_HIP(hipSetDevice(gpu->device));
-    CG_TRY(order_pack_behind_decode(stream));
-    const ImageDesc *dd = static_cast<const ImageDesc *>(dev_descs.ptr);
-    const uint32_t n = uint32_t(count);
-    const uint32_t step = chunk ? std::min(chunk, n) : n;
-    if (preprocess_mode == 2 && host_fallbacks == 0)
-        CG_HIP(launch_scan(static_cast<const ScanDesc *>(scan_descs.ptr), n, max_tiles, stream));
-    for (uint32_t at = 0; at < n; at += step) {
-        const uint32_t m = std::min(step, n - at);
-        const HuffLdsPlan plan = plan_huffman(max_intervals, m, max_l2, max_span, false, reduced_wave_cap());
-        ReducedTarget part = target;
-        part.dst = target.dst + uint64_t(at) * target.image_stride;
-        CG_HIP(launch_reduced(dd + at, m, max_intervals, plan, hs, vs, part, stream));
-    }
-    last_kernel = COMPEG_KERNEL_REDUCED;
-    decode_recorded = true; // (as in decode_planes)
     return note_pack(stream);
 }
 

@@ -147,12 +147,11 @@ struct compeg_decoder {
     uint32_t deferred_expected = 0;
 
     // may_defer: the caller will wait for the stream and then call finish_deferred(img)
-    // planes (compeg_hip.h, "Planar YCbCr output"): upload and preprocess as ever, then the planes decode into the
-    // caller's memory in place of the RGBA decode -- the texture, its extent and what the packs read are left alone
-    // reduced (compeg_hip.h, "Reduced-size decode"): the same road with the 1/8-scale decode at its end; at most one of
-    // the two targets is given
+    // into (kernels.h; compeg_hip.h, "Planar YCbCr output", "Reduced-size decode"): upload and preprocess as ever, then
+    // that decode into the caller's memory in place of the RGBA decode -- the texture, its extent and what the packs read
+    // are left alone
     compeg::Status enqueue(const compeg::ImageData &img, hipStream_t stream, bool *changed, bool may_defer = false,
-                           const compeg::PlanesTarget *planes = nullptr, const compeg::ReducedTarget *reduced = nullptr);
+                           const compeg::CallerDecode *into = nullptr);
     compeg::Status finish_deferred(const compeg::ImageData &img, hipStream_t stream);
     // Tensor output (compeg_hip.h): the last image's corner of `out`, packed on `stream` behind the last decode; the next
     // decode waits for it.  spec and dst: checked by the caller.
@@ -278,13 +277,11 @@ struct compeg_batch {
     std::vector<std::unique_ptr<compeg::ImageData>> feed_fresh;
     compeg::Status decode(hipStream_t stream);
     bool output_decoded = false; // `out` holds a decode of the images uploaded last
-    // Planes decode (compeg_hip.h, "Planar YCbCr output"): every image into the caller's memory, image i at
-    // target.dst + i * target.image_stride; one size and one sampling (hs x vs; 1 x 0: grayscale), checked by the caller
-    // like target.  Chunks and preprocessing mode 2 as in decode(); ordered like a pack; no timing events; `out` untouched.
-    compeg::Status decode_planes(const compeg::PlanesTarget &target, uint32_t hs, uint32_t vs, hipStream_t stream);
-    // Reduced decode (compeg_hip.h, "Reduced-size decode"): decode_planes' loop with the 1/8-scale kernels; everything
-    // said there holds here.
-    compeg::Status decode_reduced(const compeg::ReducedTarget &target, uint32_t hs, uint32_t vs, hipStream_t stream);
+    // A decode into the caller's memory (kernels.h: planes_decode, reduced_decode; compeg_hip.h, "Planar YCbCr output",
+    // "Reduced-size decode"): every image, image i at the target's dst + i * image_stride; one size and one sampling
+    // (hs x vs; 1 x 0: grayscale), checked by the caller like the target.  Chunks and preprocessing mode 2 as in decode();
+    // ordered like a pack; no timing events; `out` untouched.
+    compeg::Status decode_into(const compeg::CallerDecode &into, uint32_t hs, uint32_t vs, hipStream_t stream);
     // Tensor output (compeg_hip.h): every image's output (all of one size: checked by the caller, like spec and dst)
     compeg::Status pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream);
     // ... and every pack's ordering, in the batch's own scheme (it records decode_done only when a stream changes): `stream`
