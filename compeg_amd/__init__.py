@@ -17,7 +17,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
+from ._lib import (CropSpec, E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
                    LIB_PATH, METADATA_BYTES, Error, FilterSpec, LumaSpec, NhwcSpec, OrientedRegion, PlanesLayout, PlanesSpec, Rect, ReducedSpec, Region, ResizeSpec,
                    TensorSpec, check,
                    lib)
@@ -28,14 +28,15 @@ __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Te
            "region_tensor_shape", "FILTER_KERNELS", "FilterSpec", "filtered_tensor_shape", "ORIENTATIONS", "OrientedRegion",
            "orient_rect", "oriented_tensor_shape", "NhwcSpec", "nhwc_tensor_shape", "LumaSpec", "LUMA_WEIGHTS",
            "luma_tensor_shape", "PlanesSpec", "PlanesLayout", "PLANES_FORMATS", "PLANES_CHROMA", "planes_shape",
-           "ReducedSpec", "REDUCED_FORMATS", "reduced_shape"]
+           "ReducedSpec", "REDUCED_FORMATS", "reduced_shape", "CropSpec", "CROP_FORMATS", "crop_shape"]
 
 
 # compeg_decoder_last_kernel / compeg_batch_last_kernel (include/compeg_hip.h: COMPEG_KERNEL_*).  KERNEL_NAMES: the RGBA
 # routes and the planes decode, ten names (tests/test_planes_stream.py pins the count); ALL_KERNEL_NAMES: every value
-# last_kernel() can give, the reduced decode's (COMPEG_KERNEL_REDUCED = 10) behind them.
+# last_kernel() can give, the reduced decode's (COMPEG_KERNEL_REDUCED = 10) and the cropped decode's
+# (COMPEG_KERNEL_CROPPED = 11) behind them.
 KERNEL_NAMES = ("none", "fused", "pair", "coop_team", "generic", "split", "fused_layout", "fused_stream", "walk_mcu", "planes")
-ALL_KERNEL_NAMES = KERNEL_NAMES + ("reduced",)
+ALL_KERNEL_NAMES = KERNEL_NAMES + ("reduced", "cropped")
 
 
 def version():
@@ -469,6 +470,32 @@ def reduced_shape(width, height, format="rgba", pitch=None):
     return ow.value, oh.value, pt.value, total.value
 
 
+# Cropped decode (include/compeg_hip.h: COMPEG_CROP_*): formats by name
+CROP_FORMATS = {"rgba": 0, "rgb_planar": 1}
+
+
+def _crop_spec(rect, format, pitch):
+    """compeg_crop_spec from a rectangle (x, y, width, height) in pixels of the image and a format's name (or the header's
+    number, which the library checks); pitch: None or 0 = tight."""
+    if isinstance(format, str) and format not in CROP_FORMATS:
+        raise Error(f"unknown crop format {format!r} (one of {', '.join(CROP_FORMATS)})")
+    spec = CropSpec()
+    spec.x, spec.y, spec.width, spec.height = (int(v) for v in rect)
+    spec.format = CROP_FORMATS[format] if isinstance(format, str) else format
+    spec.pitch = int(pitch or 0)
+    return spec
+
+
+def crop_shape(width, height, rect, format="rgba", pitch=None):
+    """(pitch, total_bytes) of the cropped decode of rect = (x, y, w, h) out of one width x height image --
+    compeg_crop_shape; no device needed.  The rectangle must be non-empty and inside the image.  "rgba": rows of 4 w bytes
+    at `pitch` (a multiple of 4, None = tight); "rgb_planar": a tight [3, h, w] u8 block."""
+    spec = _crop_spec(rect, format, pitch)
+    pt, total = C.c_uint32(), C.c_uint64()
+    check(lib.compeg_crop_shape(C.byref(spec), width, height, C.byref(pt), C.byref(total)))
+    return pt.value, total.value
+
+
 def _host_view(data):
     a = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
     return np.ascontiguousarray(a)
@@ -777,6 +804,22 @@ class Decoder:
         else:
             check(lib.compeg_decoder_decode_reduced(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
 
+    def decode_cropped(self, data, dst, rect, format="rgba", pitch=None, hip_stream=None, blocking=False):
+        """Extension (compeg_decoder_decode_cropped): uploads and preprocesses `data` as enqueue does and records, on
+        hip_stream (None or 0 = the gpu's stream), a decode of rect = (x, y, w, h) -- pixels of the image, non-empty,
+        inside it -- into caller-owned device memory as crop_shape lays it out: pixel (i, j) is pixel (x + i, y + j) of the
+        RGBA decode, byte for byte.  Restart intervals without an MCU in the rectangle are not decoded.  dst: (address,
+        nbytes), a tensor, or a __cuda_array_interface__ object of at least total_bytes.  The texture and what the packs
+        read are not touched.  Returns without waiting; blocking=True (the gpu's stream only) waits for the decode."""
+        spec = _crop_spec(rect, format, pitch)
+        addr, nbytes = _device_range(dst)
+        if blocking:
+            if hip_stream:
+                raise Error("decode_cropped: blocking=True records on the gpu's own stream")
+            check(lib.compeg_decoder_decode_cropped_blocking(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes))
+        else:
+            check(lib.compeg_decoder_decode_cropped(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream or None)))
+
     def last_warning(self):
         return lib.compeg_decoder_last_warning(self._h).decode()
 
@@ -984,6 +1027,15 @@ class Batch:
         spec = _reduced_spec(format, pitch)
         addr, nbytes = _device_range(dst)
         check(lib.compeg_batch_decode_reduced(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
+
+    def decode_cropped(self, dst, rect, format="rgba", pitch=None, hip_stream=None):
+        """Extension (compeg_batch_decode_cropped): records, on hip_stream (None or 0 = the gpu's stream), a decode of
+        rect = (x, y, w, h), one rectangle for all of the last upload's images (all of one size and sampling), into
+        caller-owned device memory, image i at i * total_bytes of crop_shape.  dst: (address, nbytes), a tensor, or a
+        __cuda_array_interface__ object.  The RGBA outputs are not touched; wait() covers it."""
+        spec = _crop_spec(rect, format, pitch)
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_batch_decode_cropped(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream or None)))
 
     def wait(self):
         check(lib.compeg_batch_wait(self._h))

@@ -1800,7 +1800,7 @@ const char *sampling_name(uint32_t components, uint32_t hs, uint32_t vs)
     return hs == 2 && vs == 1 ? "4:2:2" : hs == 1 && vs == 1 ? "4:4:4" : hs == 1 && vs == 2 ? "4:4:0" : hs == 2 && vs == 2 ? "4:2:0" : "unknown";
 }
 
-// Decodes into the caller's memory (planes, reduced), every entry point of every output down one road (decode_to_caller).
+// Decodes into the caller's memory (planes, reduced, cropped), every entry point of every output down one road (decode_to_caller).
 // What such a decode is laid out for: a decoder's image, or the one size and sampling all images of a batch share.
 struct DecodeFacts {
     uint32_t width, height, components, hs, vs; // (hs x vs: the file's luma sampling factors)
@@ -2149,6 +2149,132 @@ int compeg_decoder_decode_reduced_blocking(compeg_decoder *dec, const compeg_ima
                                            size_t dst_bytes)
 {
     return decode_to_caller(dec, img, ReducedOutput{spec}, device_dst, dst_bytes, nullptr, true);
+}
+
+} // extern "C"
+
+/* ---- Cropped decode --------------------------------------------------------- */
+
+namespace {
+
+struct CropLayout {
+    uint32_t pitch;
+    uint64_t total;
+};
+
+// compeg_crop_spec as the header has it, laid out against a width x height image: 0 with *out filled in, or the error
+// recorded.  (The texts name values, not the header's macros.)
+int crop_layout(const compeg_crop_spec *spec, uint32_t width, uint32_t height, CropLayout *out)
+{
+    if (!spec)
+        return fail(COMPEG_E_INVALID_ARG, "spec is NULL");
+    if (spec->format > COMPEG_CROP_RGB_PLANAR)
+        return fail(COMPEG_E_INVALID_ARG, ("crop spec: format " + std::to_string(spec->format) + " is neither 0 (rgba) nor 1 (rgb planar)").c_str());
+    if (spec->reserved[0] != 0u || spec->reserved[1] != 0u)
+        return fail(COMPEG_E_INVALID_ARG, ("crop spec: reserved is " + std::to_string(spec->reserved[0]) + ", " + std::to_string(spec->reserved[1]) +
+                                           ", it must be 0").c_str());
+    if (width == 0 || height == 0)
+        return fail(COMPEG_E_INVALID_ARG, "crop: the image has no pixels");
+    const std::string rect = std::to_string(spec->width) + "x" + std::to_string(spec->height) + " at (" + std::to_string(spec->x) + ", " +
+                             std::to_string(spec->y) + ")";
+    if (spec->width == 0 || spec->height == 0)
+        return fail(COMPEG_E_INVALID_ARG, ("crop spec: the rectangle " + rect + " is empty").c_str());
+    if (uint64_t(spec->x) + spec->width > width || uint64_t(spec->y) + spec->height > height)
+        return fail(COMPEG_E_INVALID_ARG, ("crop spec: the rectangle " + rect + " reaches beyond the image's " + std::to_string(width) + "x" +
+                                           std::to_string(height)).c_str());
+    CropLayout l;
+    if (spec->format == COMPEG_CROP_RGB_PLANAR) {
+        if (spec->pitch != 0u)
+            return fail(COMPEG_E_INVALID_ARG, ("crop spec: pitch " + std::to_string(spec->pitch) + " with the planar format, whose rows are tight (pitch 0)").c_str());
+        l.pitch = spec->width;
+        l.total = 3ull * spec->width * spec->height;
+    } else {
+        const uint64_t row = 4ull * spec->width;
+        if (spec->pitch != 0u && (spec->pitch < row || spec->pitch % 4u != 0u))
+            return fail(COMPEG_E_INVALID_ARG, ("crop spec: pitch " + std::to_string(spec->pitch) + " is not a multiple of 4 at or above the row's " +
+                                               std::to_string(row) + " bytes").c_str());
+        l.pitch = spec->pitch ? spec->pitch : uint32_t(row);
+        l.total = uint64_t(l.pitch) * spec->height;
+    }
+    *out = l;
+    return COMPEG_OK;
+}
+
+// (mcu_w x mcu_h: the image's MCU in pixels.)  The rectangle in MCUs, once for the launch: the kernels' touch test and
+// their per-MCU test read it.
+CropTarget crop_target(const compeg_crop_spec &spec, const CropLayout &l, uint32_t mcu_w, uint32_t mcu_h, void *device_dst)
+{
+    CropTarget t{};
+    t.dst = static_cast<uint8_t *>(device_dst);
+    t.image_stride = l.total;
+    t.x = spec.x;
+    t.y = spec.y;
+    t.width = spec.width;
+    t.height = spec.height;
+    t.pitch = l.pitch;
+    t.format = spec.format;
+    t.mx0 = spec.x / mcu_w;
+    t.mx1 = (spec.x + spec.width - 1u) / mcu_w + 1u;
+    t.my0 = spec.y / mcu_h;
+    t.my1 = (spec.y + spec.height - 1u) / mcu_h + 1u;
+    return t;
+}
+
+struct CroppedOutput {
+    using Target = CropTarget;
+    static constexpr const char *kPrefix = "crop";
+    const compeg_crop_spec *spec;
+    int target_for(const DecodeFacts &f, void *device_dst, size_t dst_bytes, CropTarget *target) const
+    {
+        CropLayout l;
+        int rc = crop_layout(spec, f.width, f.height, &l);
+        if (rc == COMPEG_OK && spec->format == COMPEG_CROP_RGBA && reinterpret_cast<uintptr_t>(device_dst) % 4u != 0u)
+            rc = fail(COMPEG_E_INVALID_ARG, "crop: the rgba destination's address is not a multiple of 4");
+        if (rc == COMPEG_OK)
+            rc = check_destination(kPrefix, device_dst, dst_bytes, l.total, f.images);
+        if (rc == COMPEG_OK) {
+            const bool gray = f.components == 1;
+            *target = crop_target(*spec, l, 8u * (gray ? 1u : f.hs), 8u * (gray ? 1u : f.vs), device_dst);
+        }
+        return rc;
+    }
+    static CallerDecode decode(const CropTarget &target) { return cropped_decode(target); }
+};
+
+} // namespace
+
+extern "C" {
+
+int compeg_crop_shape(const compeg_crop_spec *spec, uint32_t image_width, uint32_t image_height, uint32_t *pitch, uint64_t *total_bytes)
+{
+    return guarded([&] {
+        CropLayout l;
+        const int rc = crop_layout(spec, image_width, image_height, &l);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (pitch)
+            *pitch = l.pitch;
+        if (total_bytes)
+            *total_bytes = l.total;
+        return ok();
+    });
+}
+
+int compeg_batch_decode_cropped(compeg_batch *batch, const compeg_crop_spec *spec, void *device_dst, size_t dst_bytes, void *hip_stream)
+{
+    return decode_to_caller(batch, nullptr, CroppedOutput{spec}, device_dst, dst_bytes, hip_stream);
+}
+
+int compeg_decoder_decode_cropped(compeg_decoder *dec, const compeg_image *img, const compeg_crop_spec *spec, void *device_dst,
+                                  size_t dst_bytes, void *hip_stream)
+{
+    return decode_to_caller(dec, img, CroppedOutput{spec}, device_dst, dst_bytes, hip_stream);
+}
+
+int compeg_decoder_decode_cropped_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_crop_spec *spec, void *device_dst,
+                                           size_t dst_bytes)
+{
+    return decode_to_caller(dec, img, CroppedOutput{spec}, device_dst, dst_bytes, nullptr, true);
 }
 
 } // extern "C"

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "compeg_hip.h"
+#include "crop_types.h"
 #include "device_types.h"
 #include "planes_types.h"
 #include "reduced_types.h"
@@ -218,6 +219,14 @@ uint32_t reduced_wave_cap();
 hipError_t launch_reduced(const ImageDesc *descs, uint32_t images, uint32_t max_intervals, const HuffLdsPlan &plan, uint32_t hs, uint32_t vs,
                           const ReducedTarget &target, hipStream_t stream);
 
+// Cropped decode (crop_kernels.hip, crop_body.h): one rectangle of every image, pixel for pixel the RGBA decode's, into
+// the caller's memory as `target` lays it out; a lane per restart interval behind whole windows, and no work for an
+// interval, a wave or a workgroup without an MCU in the rectangle.  hs x vs as for launch_planes; plan: plan_huffman's
+// with wave_cap = crop_wave_cap.  target: validated by the caller.
+uint32_t crop_wave_cap(uint32_t hs, uint32_t vs);
+hipError_t launch_cropped(const ImageDesc *descs, uint32_t images, uint32_t max_intervals, const HuffLdsPlan &plan, uint32_t hs, uint32_t vs,
+                          const CropTarget &target, hipStream_t stream);
+
 // A decode into the caller's memory, as the runtime's one road for them takes it (compeg_decoder::enqueue,
 // compeg_batch::decode_into): how to plan it, how to launch it, what to record.  A further output of this shape is a
 // further maker below, nothing in the runtime.
@@ -247,6 +256,10 @@ inline CallerDecode reduced_decode(const ReducedTarget &target)
 {
     return CallerDecode{&target, launch_caller_decode<ReducedTarget, launch_reduced>, false,
                         [](uint32_t, uint32_t) { return reduced_wave_cap(); }, COMPEG_KERNEL_REDUCED};
+}
+inline CallerDecode cropped_decode(const CropTarget &target)
+{
+    return CallerDecode{&target, launch_caller_decode<CropTarget, launch_cropped>, true, crop_wave_cap, COMPEG_KERNEL_CROPPED};
 }
 
 #if defined(CG_AC_STAMPS)

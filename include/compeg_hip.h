@@ -202,6 +202,8 @@ int compeg_decoder_last_stage_times(const compeg_decoder *dec, compeg_stage_time
                                        (compeg_*_decode_planes), a lane per restart interval */
 #define COMPEG_KERNEL_REDUCED 10     /* decode_reduced_422 / _444 / _440 / _420 / _gray_kernel: a reduced decode
                                        (compeg_*_decode_reduced), a lane per restart interval */
+#define COMPEG_KERNEL_CROPPED 11     /* decode_cropped_422 / _444 / _440 / _420 / _gray_kernel: a cropped decode
+                                       (compeg_*_decode_cropped), a lane per restart interval that touches the rectangle */
 int compeg_decoder_last_kernel(const compeg_decoder *dec);
 /* Extension: on != 0 moves the scan preprocessing of every following decode
  * from the host (the reference's data flow, default) to the device-side scan
@@ -870,6 +872,76 @@ int compeg_batch_decode_reduced(compeg_batch *batch, const compeg_reduced_spec *
 int compeg_decoder_decode_reduced(compeg_decoder *dec, const compeg_image *img, const compeg_reduced_spec *spec, void *device_dst,
                                   size_t dst_bytes, void *hip_stream);
 int compeg_decoder_decode_reduced_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_reduced_spec *spec,
+                                           void *device_dst, size_t dst_bytes);
+
+/* ---- Cropped decode (extension) -----------------------------------------------
+ * A fourth kind of decode: one rectangle of the image, written into caller-owned device memory that holds the
+ * rectangle and nothing else.  What nvJPEG calls a decode ROI and libjpeg-turbo jpeg_crop_scanline: a detector's box, a
+ * fixed region of a fixed camera, without the full image in between.  A restart interval none of whose MCUs has a pixel
+ * in the rectangle is not decoded, nor read: on restart-interval MJPEG a small rectangle costs a small part of the
+ * decode.  New entry points beside the old ones: the RGBA output, compeg_decoder_output / _read_output, and what the
+ * tensor packs see as "the last decode" are not touched by a cropped decode, and without these calls nothing behaves
+ * differently.
+ *
+ * The rectangle (x, y, width, height) is in pixels of the W x H image.  It must be non-empty and lie wholly inside the
+ * image: width >= 1, height >= 1, x + width <= W, y + height <= H.  x and y need not be aligned to anything.
+ *
+ * Output pixel (i, j), 0 <= i < width, 0 <= j < height, is pixel (x + i, y + j) of the RGBA decode of the same file
+ * (compeg_decoder_decode / compeg_batch_decode), byte for byte, with A = 255: the same transform, chroma replicated to
+ * the nearest neighbour, the same integer colour step.  Everything that shapes that decode acts here exactly as there:
+ * the entropy quirks Q1, Q2, Q4 and Q5 unless COMPEG_PARSE_STANDARD_ENTROPY, the DC predictor's 32-bit wrap, an
+ * interval beyond the scan's restart markers decoding from the scan's first word, grayscale files giving R = G = B.
+ *
+ * MCUs behind the last complete restart interval are not decoded and their bytes in the destination are NOT WRITTEN:
+ * the memory is the caller's, its previous contents stay.  Nothing outside the rectangle's bytes is ever written -- not
+ * the rest of a row inside its pitch, not a byte in front of an image or behind it.
+ *
+ * format:
+ *   RGBA        interleaved R G B A, 4 bytes a pixel, A = 255.  pitch: bytes from row to row, 0 = tight (4 width).
+ *               The destination's address and the pitch must be multiples of 4 (COMPEG_E_INVALID_ARG otherwise).
+ *   RGB_PLANAR  [3, height, width] bytes, tight, any address: a CHW u8 tensor as it stands.  pitch must be 0.
+ * reserved must be 0. */
+#define COMPEG_CROP_RGBA 0
+#define COMPEG_CROP_RGB_PLANAR 1
+typedef struct compeg_crop_spec {
+    uint32_t x, y, width, height; /* the rectangle, in pixels of the image */
+    uint32_t format;              /* COMPEG_CROP_* */
+    uint32_t pitch;               /* RGBA: bytes from row to row, 0 = tight; RGB_PLANAR: 0 */
+    uint32_t reserved[2];         /* 0 */
+} compeg_crop_spec;               /* 32 bytes */
+/* No device needed: checks the spec against an image_width x image_height image and gives the pitch that will be used
+ * (RGB_PLANAR: width) and one image's bytes (RGBA: pitch * height, the last row at its full pitch; RGB_PLANAR:
+ * 3 * width * height).  Either output may be NULL.  COMPEG_E_INVALID_ARG, with a message that states the values, for: a
+ * NULL spec, a format out of range, reserved not 0, an image without pixels, an empty rectangle, a rectangle that
+ * reaches beyond the image, RGB_PLANAR with a pitch, an RGBA pitch below 4 * width or not a multiple of 4.  Nothing is
+ * written on failure. */
+int compeg_crop_shape(const compeg_crop_spec *spec, uint32_t image_width, uint32_t image_height, uint32_t *pitch,
+                      uint64_t *total_bytes);
+/* The images of the batch's last upload, image i to device_dst + i * total_bytes, one rectangle for all of them.  All
+ * images must have one size and one sampling (COMPEG_E_INVALID_ARG with a message otherwise, as
+ * compeg_batch_decode_planes asks); dst_bytes below count * total_bytes is refused before anything is launched (the
+ * message names both numbers).  Records on hip_stream (NULL = the gpu's stream) and returns without waiting;
+ * compeg_batch_wait covers it.  compeg_batch_set_chunk and the three preprocessing modes work as for
+ * compeg_batch_decode.  Any number of calls, with different specs, in any order with the batch's other decodes, after
+ * one upload.  It records none of the batch's timing events.  Ordering is the tensor packs': a cropped decode on another
+ * stream than the batch's previous work waits for that work, and what the batch does next on another stream waits for
+ * it.  compeg_batch_last_kernel then says COMPEG_KERNEL_CROPPED.
+ * Known limits: the scan preprocessing still reads the whole entropy-coded segment, since every interval's start comes
+ * from it -- the saving is in the decode kernel; a touched interval is walked from its start up to its last MCU in the
+ * rectangle, so a file without DRI or with long intervals saves little; a lane per restart interval on every launch
+ * (no cooperative, walk or streamed-window form); one rectangle a call; no mixed sizes or samplings; no cropped planes
+ * or reduced output; the tensor packs do not read a caller's image. */
+int compeg_batch_decode_cropped(compeg_batch *batch, const compeg_crop_spec *spec, void *device_dst, size_t dst_bytes,
+                                void *hip_stream);
+/* One image: uploads and preprocesses as compeg_decoder_enqueue does (host or device preprocessing), records the
+ * cropped decode on hip_stream (NULL = the gpu's stream) and returns without waiting.  The decoder's texture, its
+ * extent and what the packs read stay those of the last RGBA decode.  To wait: synchronise hip_stream, or call
+ * compeg_decoder_decode_cropped_blocking, which does.  The decoder's next enqueue or pack on another stream waits for
+ * the cropped decode, as this call waits for the decoder's previous work.  compeg_decoder_last_kernel then says
+ * COMPEG_KERNEL_CROPPED. */
+int compeg_decoder_decode_cropped(compeg_decoder *dec, const compeg_image *img, const compeg_crop_spec *spec, void *device_dst,
+                                  size_t dst_bytes, void *hip_stream);
+int compeg_decoder_decode_cropped_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_crop_spec *spec,
                                            void *device_dst, size_t dst_bytes);
 
 #if defined(__GNUC__)

@@ -140,6 +140,20 @@ pub struct compeg_reduced_spec {
     pub pitch: u32,
 }
 
+/// What a cropped decode writes (compeg_hip.h, "Cropped decode"): the rectangle in pixels of the image, the format and
+/// the RGBA row pitch in bytes (0 = tight); `reserved` is 0.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct compeg_crop_spec {
+    pub x: u32,
+    pub y: u32,
+    pub width: u32,
+    pub height: u32,
+    pub format: u32,
+    pub pitch: u32,
+    pub reserved: [u32; 2],
+}
+
 pub const COMPEG_OK: c_int = 0;
 pub const COMPEG_E_INVALID_ARG: c_int = -1;
 pub const COMPEG_E_UNSUPPORTED: c_int = -2;
@@ -160,6 +174,9 @@ pub const COMPEG_KERNEL_FUSED_STREAM: c_int = 7;
 pub const COMPEG_KERNEL_WALK_MCU: c_int = 8;
 pub const COMPEG_KERNEL_PLANES: c_int = 9;
 pub const COMPEG_KERNEL_REDUCED: c_int = 10;
+pub const COMPEG_KERNEL_CROPPED: c_int = 11;
+pub const COMPEG_CROP_RGBA: u32 = 0;
+pub const COMPEG_CROP_RGB_PLANAR: u32 = 1;
 pub const COMPEG_REDUCED_RGBA: u32 = 0;
 pub const COMPEG_REDUCED_RGB_PLANAR: u32 = 1;
 pub const COMPEG_PLANES_PLANAR: u32 = 0;
@@ -387,5 +404,13 @@ extern "C" {
     pub fn compeg_decoder_decode_reduced(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_reduced_spec,
                                          device_dst: *mut c_void, dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
     pub fn compeg_decoder_decode_reduced_blocking(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_reduced_spec,
+                                                  device_dst: *mut c_void, dst_bytes: usize) -> c_int;
+    pub fn compeg_crop_shape(spec: *const compeg_crop_spec, image_width: u32, image_height: u32, pitch: *mut u32,
+                             total_bytes: *mut u64) -> c_int;
+    pub fn compeg_batch_decode_cropped(batch: *mut compeg_batch, spec: *const compeg_crop_spec, device_dst: *mut c_void,
+                                       dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_decoder_decode_cropped(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_crop_spec,
+                                         device_dst: *mut c_void, dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_decoder_decode_cropped_blocking(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_crop_spec,
                                                   device_dst: *mut c_void, dst_bytes: usize) -> c_int;
 }

@@ -431,6 +431,56 @@ pub fn reduced_shape(spec: &ReducedSpec, width: u32, height: u32) -> Result<Redu
     Ok(s)
 }
 
+/// The format of a cropped decode (compeg_hip.h, "Cropped decode").
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum CropFormat {
+    /// Interleaved R G B A, A = 255; address and pitch multiples of 4.
+    Rgba,
+    /// `[3, height, width]` bytes, tight: a CHW u8 tensor.
+    RgbPlanar,
+}
+
+/// What `Decoder::decode_cropped` / `Batch::decode_cropped` write: the rectangle `width x height` at `(x, y)` of the image
+/// -- non-empty, inside it -- pixel for pixel what the RGBA decode has there.  `pitch`: the RGBA rows' pitch in bytes,
+/// 0 = tight.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct CropSpec {
+    pub x: u32,
+    pub y: u32,
+    pub width: u32,
+    pub height: u32,
+    pub format: CropFormat,
+    pub pitch: u32,
+}
+
+/// `crop_shape`'s answer: the pitch in use and one image's bytes.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct CropShape {
+    pub pitch: u32,
+    pub total_bytes: u64,
+}
+
+impl CropSpec {
+    pub fn new(x: u32, y: u32, width: u32, height: u32, format: CropFormat) -> Self {
+        CropSpec { x, y, width, height, format, pitch: 0 }
+    }
+
+    fn raw(&self) -> ffi::compeg_crop_spec {
+        let format = match self.format {
+            CropFormat::Rgba => ffi::COMPEG_CROP_RGBA,
+            CropFormat::RgbPlanar => ffi::COMPEG_CROP_RGB_PLANAR,
+        };
+        ffi::compeg_crop_spec { x: self.x, y: self.y, width: self.width, height: self.height, format, pitch: self.pitch, reserved: [0; 2] }
+    }
+}
+
+/// No device needed: checks the rectangle against an `image_width x image_height` image and gives the destination's size.
+pub fn crop_shape(spec: &CropSpec, image_width: u32, image_height: u32) -> Result<CropShape> {
+    let mut s = CropShape { pitch: 0, total_bytes: 0 };
+    check(unsafe { ffi::compeg_crop_shape(&spec.raw(), image_width, image_height, &mut s.pitch, &mut s.total_bytes) })?;
+    Ok(s)
+}
+
 /// The weights of `Decoder::pack_tensor_luma` / `Batch::pack_tensor_luma` (compeg_hip.h, "Luma tensor output"): per source
 /// pixel `L = (wR R + wG G + wB B + 32768) >> 16`; the destination is `[count][1][oh][ow]`.  A grayscale frame gives its
 /// own values under any of them.
@@ -849,6 +899,27 @@ impl Decoder {
         check(ffi::compeg_decoder_decode_reduced_blocking(self.raw.as_ptr(), image.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes))
     }
 
+    /// Extension: uploads and preprocesses `image` as `enqueue` does and records, on `stream`, a decode of the spec's
+    /// rectangle into caller-owned device memory as `crop_shape` lays it out; restart intervals without an MCU in the
+    /// rectangle are not decoded.  The texture and what the packs read are not touched.  Returns without waiting:
+    /// synchronise `stream`, or use `decode_cropped_blocking`.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn decode_cropped(&mut self, image: &ImageData, spec: &CropSpec, device_dst: *mut c_void, dst_bytes: usize,
+                                 stream: Stream) -> Result<()> {
+        check(ffi::compeg_decoder_decode_cropped(self.raw.as_ptr(), image.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
+    }
+
+    /// `decode_cropped` on the gpu's own stream, and the wait for it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes.
+    pub unsafe fn decode_cropped_blocking(&mut self, image: &ImageData, spec: &CropSpec, device_dst: *mut c_void,
+                                          dst_bytes: usize) -> Result<()> {
+        check(ffi::compeg_decoder_decode_cropped_blocking(self.raw.as_ptr(), image.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes))
+    }
+
     /// Test helper (the reference's tests copy the texture to a buffer): waits and
     /// returns the image's `width x height` corner, tightly packed.
     pub fn read_output(&mut self, width: u32, height: u32) -> Result<Vec<u8>> {
@@ -1108,6 +1179,16 @@ impl Batch {
     /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
     pub unsafe fn decode_reduced(&mut self, spec: &ReducedSpec, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
         check(ffi::compeg_batch_decode_reduced(self.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
+    }
+
+    /// Extension: records a decode of the spec's rectangle, one for all of the last upload's images (all of one size and
+    /// sampling), into caller-owned device memory, image i at `i * total_bytes` of `crop_shape`.  The RGBA outputs are not
+    /// touched.  Returns without waiting; `wait` covers it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn decode_cropped(&mut self, spec: &CropSpec, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        check(ffi::compeg_batch_decode_cropped(self.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
     }
 
     /// The EXIF orientation tag (1..8) of image `index` of the last upload.

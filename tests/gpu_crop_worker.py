@@ -1,0 +1,579 @@
+"""The GPU cases of tests/test_gpu_crop.py: Decoder.decode_cropped / Batch.decode_cropped into torch memory, every byte
+against tests/crop_stream.py -- the destination between sentinels and over a pre-fill, so that what must not be written
+shows.  Run in one process of their own that imports torch before the library (tests/gpu_luma_worker.py: why).
+
+    python tests/gpu_crop_worker.py RESULTS.json [substring of the case names to run]
+
+Every decode asserts last_kernel() == "cropped".  RESULTS.json: case name -> null, or what went wrong; "wall_s"."""
+import io
+import json
+import os
+import sys
+import time
+import traceback
+
+import numpy as np
+
+torch = ca = ps = crs = cs = gs = orc = ss = gpu = None   # set by main(): torch first
+GUARD, SENTINEL, PREFILL = 256, 0x5C, 0xA5
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+FAMILIES = ("dc_cats", "dc_hostile", "q1_underflow", "dc_wrap", "dc_sweep", "saturated", "gamut", "random_dense")   # (the reduced worker's)
+
+
+class Dest:
+    """n images' worth of destination inside one torch block: sentinels, `shift` bytes, the images over a pre-fill, sentinels."""
+
+    def __init__(self, total, n=1, shift=0):
+        self.total, self.n, self.shift = total, n, shift
+        self.block = torch.full((GUARD + shift + total * n + GUARD,), SENTINEL, dtype=torch.uint8, device="cuda")
+        self.block[GUARD + shift:GUARD + shift + total * n] = PREFILL
+        torch.cuda.synchronize()
+
+    @property
+    def range(self):
+        return (self.block.data_ptr() + GUARD + self.shift, self.total * self.n)
+
+    def read(self, what):
+        """[n, total] bytes; the sentinels checked."""
+        torch.cuda.synchronize()
+        host = self.block.cpu().numpy()
+        body = host[GUARD + self.shift:GUARD + self.shift + self.total * self.n]
+        assert (host[:GUARD + self.shift] == SENTINEL).all() and (host[-GUARD:] == SENTINEL).all(), f"{what}: a sentinel was written"
+        return body.reshape(self.n, self.total)
+
+
+def _geometry(w, h, rect, format, pitched):
+    pitch = (4 * rect[2] + 15) // 16 * 16 + 16 if pitched and format == "rgba" else None
+    mine = crs.shape(w, h, rect, format, pitch)
+    assert ca.crop_shape(w, h, rect, format, pitch) == mine
+    return pitch, mine[1]
+
+
+def _want(full, rect, format, pitch, total):
+    return crs.destination(full[0], full[1], rect, format, pitch, before=np.full(total, PREFILL, dtype=np.uint8))
+
+
+def _compare(got, want, what):
+    bad = np.flatnonzero(got != want)
+    assert not bad.size, f"{what}: {bad.size} of {want.size} bytes differ, first at {bad[0]}: {got[bad[0]]} != {want[bad[0]]}"
+
+
+def _shift(format, odd):
+    """Bytes behind the 256-byte guard: the rgba destination needs a multiple of 4, the planar one takes any address."""
+    return (4 if format == "rgba" else 1) if odd else 0
+
+
+def decoder_case(f, rect, format="rgba", pitched=False, odd=False, device=False, full=None, dec=None, blocking=True):
+    full = full if full is not None else crs.frame_rgba(f, ca=ca)
+    pitch, total = _geometry(f.w, f.h, rect, format, pitched)
+    dec = dec or ca.Decoder(gpu)
+    dec.set_device_preprocess(device)
+    dst = Dest(total, 1, _shift(format, odd))
+    img = ca.ImageData(f.jpeg(), **f.image_kw())
+    if blocking:
+        dec.decode_cropped(img, dst.range, rect, format, pitch, blocking=True)
+    else:
+        s = torch.cuda.Stream()
+        dec.decode_cropped(img, dst.range, rect, format, pitch, hip_stream=s.cuda_stream)
+        s.synchronize()
+    what = (f"{f.name}: Decoder, {rect}, {format}, {'pitched' if pitched else 'tight'}, {'odd' if odd else 'aligned'}, "
+            f"{'device' if device else 'host'} preprocessing")
+    assert dec.last_kernel() == "cropped", f"{what}: last_kernel() = {dec.last_kernel()}"
+    _compare(dst.read(what)[0], _want(full, rect, format, pitch, total), what)
+    return dec
+
+
+def batch_case(frames, rect, format="rgba", pitched=False, odd=False, mode=0, chunk=0, fulls=None, batch=None):
+    f = frames[0]
+    pitch, total = _geometry(f.w, f.h, rect, format, pitched)
+    if batch is None:
+        batch = ca.Batch(gpu)
+        batch.set_device_preprocess(mode)
+        batch.upload([ca.ImageData(x.jpeg(), **x.image_kw()) for x in frames])
+    batch.set_chunk(chunk)
+    # (image i lies at i * total: with an rgba destination every image's base is a multiple of 4, since the pitch is)
+    dst = Dest(total, len(frames), _shift(format, odd))
+    batch.decode_cropped(dst.range, rect, format, pitch)
+    batch.wait()
+    what = f"{f.name} x{len(frames)}: Batch, {rect}, {format}, {'pitched' if pitched else 'tight'}, {'odd' if odd else 'aligned'}, mode {mode}, chunk {chunk}"
+    assert batch.last_kernel() == "cropped", f"{what}: last_kernel() = {batch.last_kernel()}"
+    got = dst.read(what)
+    for i, x in enumerate(frames):
+        _compare(got[i], _want(fulls[i] if fulls else crs.frame_rgba(x, ca=ca), rect, format, pitch, total), f"{what}, image {i}")
+    return batch
+
+
+# ---- the cases -------------------------------------------------------------------------------------------------------
+
+def cut_edges_and_intervals(layout):
+    """324 x 70 at every DRI of the table, every rectangle of the list: one decoder for all, both formats, tight and pitched,
+    aligned and not, host and device preprocessing; and per DRI a batch of three in each of the three preprocessing modes,
+    every rectangle through one of them with chunks of 0 (all) or 2."""
+    dec = ca.Decoder(gpu)
+    w, h = crs.SIZE
+    n = 0
+    for ri in crs.DRIS[layout]:
+        frames = [ps.sized(layout, w, h, ri, standard=ri % 2 == 0, seed=s + ri) for s in (1, 50, 90)]
+        fulls = [crs.frame_rgba(x) for x in frames]
+        assert fulls[0][1].all()
+        batches = []
+        for mode in (0, 1, 2):
+            b = ca.Batch(gpu)
+            b.set_device_preprocess(mode)
+            b.upload([ca.ImageData(x.jpeg(), **x.image_kw()) for x in frames])
+            batches.append(b)
+        for rect in crs.RECTS:
+            n += 1
+            format = crs.FORMATS[n % 2]
+            decoder_case(frames[0], rect, format, pitched=n % 3 == 0, odd=n % 4 < 2, device=n % 4 == 1, full=fulls[0], dec=dec)
+            decoder_case(frames[0], rect, crs.FORMATS[(n + 1) % 2], pitched=n % 3 != 0, odd=n % 4 >= 2, device=n % 4 != 1, full=fulls[0], dec=dec)
+            batch_case(frames, rect, format, pitched=n % 2 == 0, odd=n % 3 == 0, mode=n % 3, chunk=n % 2 * 2, fulls=fulls, batch=batches[n % 3])
+
+
+def skipped_waves_and_workgroups():
+    """640 x 384 4:2:2 at DRI 1: 1920 intervals, 40 to an MCU row, more than one workgroup at any wave cap up to 16.  One
+    launch each: a rectangle inside MCU rows 10 .. 12 (some waves of a workgroup touched, others not), one in the last two
+    MCU rows (the first workgroup untouched), one pixel; then the same through a batch of two."""
+    f = ps.sized("422", 640, 384, 1, seed=11)
+    assert f.intervals == 1920 and f.mcus_w == 40
+    full = crs.frame_rgba(f)
+    rects = ((100, 85, 200, 19), (3, 370, 630, 14), (333, 200, 1, 1))
+    dec = ca.Decoder(gpu)
+    for n, rect in enumerate(rects):
+        decoder_case(f, rect, crs.FORMATS[n % 2], pitched=n == 0, odd=n == 1, device=n == 2, full=full, dec=dec, blocking=n != 1)
+        decoder_case(f, rect, crs.FORMATS[(n + 1) % 2], full=full, dec=dec)
+    batch = None
+    for n, rect in enumerate(rects):
+        batch = batch_case([f, f], rect, crs.FORMATS[n % 2], fulls=[full, full], chunk=n % 2, batch=batch)
+
+
+def undecoded_tail():
+    """Nine MCUs at DRI 4 in every sampling: the ninth lies behind the last complete interval and keeps the pre-fill --
+    rectangles with it inside, of nothing else, and away from it."""
+    for layout in ps.SAMPLINGS:
+        hs, vs = ps.SAMPLINGS[layout]
+        mw, mh = 8 * hs, 8 * (vs if layout != "gray" else 1)
+        f = ps.sized(layout, 3 * mw, 3 * mh - 1, 4, seed=2, short=3)
+        full = crs.frame_rgba(f, ca=ca)
+        assert not full[1].all() and not full[1][2 * mh:, 2 * mw:].any(), "the frame must have its last MCU behind the last complete interval"
+        dec = ca.Decoder(gpu)
+        for k, rect in enumerate(((0, 0, f.w, f.h), (2 * mw + 1, 2 * mh + 1, mw - 2, mh - 3), (1, 1, 2 * mw - 1, 2 * mh), (mw, mh, 2 * mw, 2 * mh - 1))):
+            for format in crs.FORMATS:
+                decoder_case(f, rect, format, pitched=k % 2 == 0, odd=k % 2 == 1, full=full, dec=dec)
+                want = _want(full, rect, format, None, _geometry(f.w, f.h, rect, format, False)[1])
+                if k == 1:
+                    assert (want == PREFILL).all()
+                elif k != 2:
+                    assert (want == PREFILL).sum() >= (4 if format == "rgba" else 3)
+
+
+def tiny_frames():
+    """8 x 8 and 1 x 1: the whole frame and one pixel of it."""
+    for layout in ps.SAMPLINGS:
+        for w, h in ((8, 8), (1, 1)):
+            f = ps.sized(layout, w, h, 0, seed=w)
+            full = crs.frame_rgba(f)
+            for format in crs.FORMATS:
+                decoder_case(f, (0, 0, w, h), format, odd=format == "rgb_planar", full=full)
+                decoder_case(f, (w - 1, h - 1, 1, 1), format, full=full)
+            batch_case([f, f], (0, 0, w, h), "rgba", fulls=[full, full])
+
+
+def _noise(mode):
+    from PIL import Image
+    rng = np.random.default_rng(9)
+    out = io.BytesIO()
+    if mode == "L":
+        Image.fromarray(rng.integers(0, 256, (256, 256)).astype(np.uint8), "L").save(out, "JPEG", quality=95)
+    else:
+        Image.fromarray(rng.integers(0, 256, (256, 256, 3)).astype(np.uint8), "RGB").save(out, "JPEG", quality=95, subsampling=1)
+    j = out.getvalue()
+    assert len(gs.file_scan(j)) > 6144 * 4, "the one interval must be longer than the window cap"
+    return j
+
+
+def _file_case(name, j, kw, rects, dec=None):
+    rgba, mask, (w, h, comps, hs, vs) = crs.file_rgba(ca, j, **kw)
+    img = ca.ImageData(j, **kw)
+    dec = dec or ca.Decoder(gpu)
+    for n, rect in enumerate(rects(w, h)):
+        format = crs.FORMATS[n % 2]
+        total = crs.shape(w, h, rect, format)[1]
+        dst = Dest(total)
+        dec.decode_cropped(img, dst.range, rect, format, blocking=True)
+        assert dec.last_kernel() == "cropped", name
+        _compare(dst.read(name)[0], _want((rgba, mask), rect, format, None, total), f"{name}: {rect}, {format}, {kw}")
+    return dec
+
+
+def interval_longer_than_the_window():
+    """PIL's 256 x 256 noise without DRI, grayscale and 4:2:2: one lane, global reads beyond the window cap, an interior
+    rectangle -- the lane stops behind its last MCU in it; both entropy modes."""
+    rects = lambda w, h: ((67, 45, 100, 77), (3, 2, w - 5, h - 3))
+    for std in (False, True):
+        _file_case("noise_256 L", _noise("L"), dict(allow_grayscale=True, standard_entropy=std), rects)
+        _file_case("noise_256 RGB 4:2:2", _noise("RGB"), dict(standard_entropy=std), rects)
+
+
+def coefficient_families():
+    """dc_cats, dc_hostile, q1_underflow, dc_wrap, dc_sweep, saturated, gamut, random_dense: every frame of cs.cases() in them
+    -- both entropy modes where the family has them, every sampling -- and the grayscale ones, through one decoder, with the
+    rectangle (3, 2, W - 5, H - 3)."""
+    frames = [f for f in cs.cases() if f.family in FAMILIES] + [f for f in gs.cases() if f.family in FAMILIES]
+    assert {f.family for f in frames} == set(FAMILIES) and {f.standard for f in frames} == {False, True}
+    dec = ca.Decoder(gpu)
+    for i, f in enumerate(frames):
+        full = crs.frame_rgba(f)
+        assert f.w > 5 and f.h > 3, f.name
+        rect = (3, 2, f.w - 5, f.h - 3)
+        decoder_case(f, rect, crs.FORMATS[i % 2], pitched=i % 3 == 0, odd=i % 4 == 1, full=full, dec=dec, device=i % 2 == 1)
+        if i % 5 == 0:
+            batch_case([f], rect, crs.FORMATS[(i + 1) % 2], fulls=[full], pitched=True)
+
+
+def golden_files():
+    """Every golden file the decoder accepts, against the expectation: the whole frame, an interior rectangle, the last pixel."""
+    files = ps.golden_files(ca, GOLDEN)
+    assert len(files) >= 6
+    dec = ca.Decoder(gpu)
+    for name, j, kw in files:
+        _file_case(name, j, kw, lambda w, h: ((0, 0, w, h), (w // 3, h // 4, max(1, w // 2), max(1, h // 3)), (w - 1, h - 1, 1, 1)), dec)
+
+
+def identity_with_the_cards_own_rgba():
+    """Every sampling: the cropped RGBA is the slice of the decoder's own RGBA read-back of the same file, and the texture is
+    what it was.  (The card against itself: no host arithmetic in between.)"""
+    dec = ca.Decoder(gpu)
+    w, h = crs.SIZE
+    for n, layout in enumerate(ps.SAMPLINGS):
+        f = ps.sized(layout, w, h, crs.DRIS[layout][1], seed=20 + n)
+        img = ca.ImageData(f.jpeg(), **f.image_kw())
+        dec.decode_blocking(img)
+        full = dec.read_texture(f.w, f.h)
+        for rect in ((37, 11, 150, 41), (0, 0, w, h)):
+            x, y, rw, rh = rect
+            for format in crs.FORMATS:
+                dst = Dest(crs.shape(w, h, rect, format)[1])
+                dec.decode_cropped(img, dst.range, rect, format, blocking=True)
+                assert dec.last_kernel() == "cropped"
+                assert np.array_equal(dec.read_texture(f.w, f.h), full), f"{f.name}: the cropped decode touched the texture"
+                got = crs.view(dst.read(f.name)[0], rect, format)
+                want = full[y:y + rh, x:x + rw]
+                assert np.array_equal(got, want), f"{f.name}: {rect}, {format}: {int((got != want).any(axis=2).sum())} pixels differ from the RGBA decode's"
+
+
+def batches():
+    """Three images of one size and different content: chunks of two, the three preprocessing modes, RGBA decodes and packs
+    before and after with their results unchanged, both formats one after the other, last_kernel before, between and after."""
+    for layout, (w, h, ri) in (("422", (63, 33, 4)), ("420", (47, 31, 3)), ("gray", (23, 17, 1))):
+        frames = [ps.sized(layout, w, h, ri, seed=s) for s in (1, 30, 77)]
+        fulls = [crs.frame_rgba(f) for f in frames]
+        rgba = [gs.expectation(f) if layout == "gray" else orc.ImageData(f.jpeg(), **f.image_kw()).decode() for f in frames]
+        packed_want = np.stack([np.ascontiguousarray(x[..., :3].transpose(2, 0, 1)) for x in rgba])
+        rect = (5, 3, w - 9, h - 7)
+        for mode in (0, 1, 2):
+            batch = ca.Batch(gpu)
+            batch.set_device_preprocess(mode)
+            batch.upload([ca.ImageData(f.jpeg(), **f.image_kw()) for f in frames])
+            batch.set_chunk(2)
+            batch.decode()
+            batch.wait()
+            first = batch.last_kernel()
+            assert first != "cropped"
+            packed = torch.zeros((3, 3, h, w), dtype=torch.uint8, device="cuda")
+            batch.pack_tensor(packed, dtype="u8")
+            batch.wait()
+            assert np.array_equal(packed.cpu().numpy(), packed_want), f"{layout} mode {mode}: pack before"
+            batch_case(frames, rect, "rgba", fulls=fulls, batch=batch, mode=mode, chunk=2)
+            batch_case(frames, rect, "rgb_planar", odd=True, fulls=fulls, batch=batch, mode=mode, chunk=2)
+            for i in range(3):
+                assert np.array_equal(batch.read_output(i), rgba[i]), f"{layout} mode {mode}: RGBA {i} after the cropped decodes"
+            packed.zero_()
+            batch.pack_tensor(packed, dtype="u8")
+            batch.wait()
+            assert np.array_equal(packed.cpu().numpy(), packed_want), f"{layout} mode {mode}: pack after the cropped decodes"
+            batch.decode()
+            batch.wait()
+            assert batch.last_kernel() == first
+            for i in range(3):
+                assert np.array_equal(batch.read_output(i), rgba[i]), f"{layout} mode {mode}: RGBA {i} decoded again"
+            batch_case(frames, (0, 0, w, h), "rgba", pitched=True, fulls=fulls, batch=batch, mode=mode, chunk=2)
+
+
+class Raises:
+    def __init__(self, code, *words):
+        self.code, self.words = code, words
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, kind, e, tb):
+        assert kind is not None and issubclass(kind, ca.Error), f"no error where {self.words} was expected"
+        assert e.code == self.code and all(w in str(e) for w in self.words) and "COMPEG_" not in str(e), (e.code, str(e))
+        return True
+
+
+def refusals_on_the_card():
+    """Nothing here launches; the destination keeps its pre-fill."""
+    f = ps.sized("422", 33, 17, 0)
+    img = ca.ImageData(f.jpeg())
+    rect = (4, 2, 5, 3)
+    total = crs.shape(33, 17, rect)[1]
+    assert total == 5 * 4 * 3
+    dst = Dest(total * 3, 1)
+    addr = dst.range[0]
+    dec = ca.Decoder(gpu)
+    with Raises(ca.E_INVALID_ARG, "dst_bytes", str(total - 1), str(total)):
+        dec.decode_cropped(img, (addr, total - 1), rect)
+    with Raises(ca.E_INVALID_ARG, "device_dst is NULL"):
+        dec.decode_cropped(img, (0, total), rect)
+    with Raises(ca.E_INVALID_ARG, "address", "multiple of 4"):
+        dec.decode_cropped(img, (addr + 2, total), rect)
+    with Raises(ca.E_INVALID_ARG, "pitch 16", "20 bytes"):
+        dec.decode_cropped(img, (addr, total * 3), rect, pitch=16)
+    with Raises(ca.E_INVALID_ARG, "pitch 22", "multiple of 4"):
+        dec.decode_cropped(img, (addr, total * 3), rect, pitch=22)
+    with Raises(ca.E_INVALID_ARG, "pitch 24", "planar"):
+        dec.decode_cropped(img, (addr, total * 3), rect, "rgb_planar", pitch=24)
+    with Raises(ca.E_INVALID_ARG, "format 5"):
+        dec.decode_cropped(img, (addr, total * 3), rect, 5)
+    with Raises(ca.E_INVALID_ARG, "5x0 at (4, 2)", "empty"):
+        dec.decode_cropped(img, (addr, total * 3), (4, 2, 5, 0))
+    with Raises(ca.E_INVALID_ARG, "5x3 at (29, 2)", "beyond", "33x17"):
+        dec.decode_cropped(img, (addr, total * 3), (29, 2, 5, 3))
+    with Raises(ca.E_INVALID_ARG, "5x3 at (4, 15)", "beyond", "33x17"):
+        dec.decode_cropped(img, (addr, total * 3), (4, 15, 5, 3))
+    spec = ca._crop_spec(rect, "rgba", None)
+    spec.reserved[1] = 9
+    with Raises(ca.E_INVALID_ARG, "reserved", "0, 9"):
+        ca.check(ca.lib.compeg_decoder_decode_cropped_blocking(dec._h, img._h, ca.C.byref(spec), ca.C.c_void_p(addr), total * 3))
+    with Raises(ca.E_INVALID_ARG, "NULL"):
+        ca.check(ca.lib.compeg_decoder_decode_cropped_blocking(dec._h, img._h, None, ca.C.c_void_p(addr), total * 3))
+    with Raises(ca.E_INVALID_ARG, "NULL"):
+        ca.check(ca.lib.compeg_decoder_decode_cropped_blocking(dec._h, None, ca.C.byref(ca._crop_spec(rect, "rgba", None)), ca.C.c_void_p(addr), total * 3))
+    assert dec.last_kernel() == "none"
+    batch = ca.Batch(gpu)
+    with Raises(ca.E_INVALID_ARG, "nothing uploaded"):
+        batch.decode_cropped((addr, total * 3), rect)
+    with Raises(ca.E_INVALID_ARG, "NULL"):
+        ca.check(ca.lib.compeg_batch_decode_cropped(batch._h, None, ca.C.c_void_p(addr), total * 3, None))
+    batch.upload([img, img, img])
+    with Raises(ca.E_INVALID_ARG, "dst_bytes", str(3 * total - 1), str(3 * total), "3 image"):
+        batch.decode_cropped((addr, 3 * total - 1), rect)
+    with Raises(ca.E_INVALID_ARG, "5x3 at (29, 2)", "beyond", "33x17"):
+        batch.decode_cropped((addr, total * 3), (29, 2, 5, 3))
+    with Raises(ca.E_INVALID_ARG, "address", "multiple of 4"):
+        batch.decode_cropped((addr + 1, total * 3), rect)
+    batch.upload([img, ca.ImageData(ps.sized("422", 33, 9, 0).jpeg())])
+    with Raises(ca.E_INVALID_ARG, "not all of one size", "image 1", "33x9", "33x17"):
+        batch.decode_cropped((addr, total * 3), rect)
+    batch.upload([img, ca.ImageData(ps.sized("440", 33, 17, 0).jpeg(), allow_sampling=True)])
+    with Raises(ca.E_INVALID_ARG, "not all of one sampling", "image 1", "4:4:0", "4:2:2"):
+        batch.decode_cropped((addr, total * 3), rect)
+    batch.upload([img, ca.ImageData(ps.sized("gray", 33, 17, 0).jpeg(), allow_grayscale=True)])
+    with Raises(ca.E_INVALID_ARG, "not all of one sampling", "grayscale"):
+        batch.decode_cropped((addr, total * 3), rect)
+    assert (dst.read("refusals") == PREFILL).all()
+
+
+WINDOW = "the stalled stream had drained before the consumer was issued: the case did not test the ordering"
+ORDER_RECT = (5, 3, 40, 27)
+
+
+def _u8_pack_want(rgba):
+    return np.ascontiguousarray(rgba[..., :3].transpose(2, 0, 1))
+
+
+def _batch_for_ordering(old, total):
+    """A batch that has done everything once with the old frames: every buffer has its size."""
+    batch = ca.Batch(gpu)
+    batch.upload([ca.ImageData(f.jpeg()) for f in old])
+    batch.decode()
+    batch.pack_tensor(torch.empty((2, 3, 32, 48), dtype=torch.uint8, device="cuda"), dtype="u8")
+    batch.decode_cropped(Dest(total, 2).range, ORDER_RECT, "rgb_planar")
+    batch.wait()
+    return batch
+
+
+def ordering_batch_cropped_behind_a_stalled_decode():
+    """stall(A); RGBA decode on A; cropped decode on B; pack of the RGBA outputs on C, with nothing but the library's events
+    between them: the pack reads the new frames only if the cropped decode waited for the decode and the pack for the
+    cropped decode (it orders itself behind the batch's last stream, B).  The cropped images are the new frames' too."""
+    A, B = ss.independent_pair()
+    Cs = ss.independent_of((A, B))
+    old = [ps.sized("422", 48, 32, 4, seed=s) for s in (3, 40)]
+    new = [ps.sized("422", 48, 32, 4, seed=s) for s in (60, 85)]
+    rgba = {id(f): orc.ImageData(f.jpeg()).decode() for f in old + new}
+    want_new, want_old = np.stack([_u8_pack_want(rgba[id(f)]) for f in new]), np.stack([_u8_pack_want(rgba[id(f)]) for f in old])
+    assert not np.array_equal(want_new, want_old), "the two outcomes this case must tell apart are the same"
+    pitch, total = _geometry(48, 32, ORDER_RECT, "rgb_planar", False)
+    batch = _batch_for_ordering(old, total)
+    batch.upload([ca.ImageData(f.jpeg()) for f in new])   # (the outputs still hold the old frames)
+    dst = Dest(total, 2)
+    packed = torch.full((2, 3, 32, 48), 7, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    ss.stall(A)
+    batch.decode(A.cuda_stream)
+    batch.decode_cropped(dst.range, ORDER_RECT, "rgb_planar", hip_stream=B.cuda_stream)
+    batch.pack_tensor(packed, dtype="u8", hip_stream=Cs.cuda_stream)
+    open_ = ss.window_open(A)
+    for s in (A, B, Cs):
+        s.synchronize()
+    torch.cuda.synchronize()
+    assert open_, WINDOW
+    assert batch.last_kernel() == "cropped"
+    got = dst.read("ordering, batch")
+    for i, f in enumerate(new):
+        _compare(got[i], _want(crs.frame_rgba(f), ORDER_RECT, "rgb_planar", pitch, total), f"ordering, batch: cropped image {i}")
+    assert np.array_equal(packed.cpu().numpy(), want_new), "the pack on the third stream did not read the decode on the first"
+
+
+def ordering_batch_decode_behind_a_stalled_cropped():
+    """stall(A); cropped decode on A; RGBA decode on B.  The decode on B orders itself behind the batch's last stream: while
+    A's stall runs, B has not finished.  (B's state is read first, then A's: if A was still stalled at the second look, the
+    first look was inside the stall.)  Then both results are the new frames'."""
+    A, B = ss.independent_pair()
+    old = [ps.sized("422", 48, 32, 4, seed=s) for s in (3, 40)]
+    new = [ps.sized("422", 48, 32, 4, seed=s) for s in (60, 85)]
+    pitch, total = _geometry(48, 32, ORDER_RECT, "rgba", False)
+    batch = _batch_for_ordering(old, total)
+    batch.upload([ca.ImageData(f.jpeg()) for f in new])
+    dst = Dest(total, 2)
+    torch.cuda.synchronize()
+    ss.stall(A)
+    batch.decode_cropped(dst.range, ORDER_RECT, "rgba", hip_stream=A.cuda_stream)
+    batch.decode(B.cuda_stream)
+    b_done = B.query()
+    open_ = ss.window_open(A)
+    for s in (A, B):
+        s.synchronize()
+    torch.cuda.synchronize()
+    assert open_, WINDOW
+    assert not b_done, "the RGBA decode on the second stream finished while the cropped decode's stream was stalled"
+    assert batch.last_kernel() != "cropped"
+    got = dst.read("ordering, batch")
+    for i, f in enumerate(new):
+        _compare(got[i], _want(crs.frame_rgba(f), ORDER_RECT, "rgba", pitch, total), f"ordering, batch: cropped image {i}")
+        assert np.array_equal(batch.read_output(i), orc.ImageData(f.jpeg()).decode()), f"ordering, batch: RGBA {i}"
+
+
+def ordering_decoder_cropped_behind_a_stalled_decode():
+    """stall(A); enqueue(new) on A; decode_cropped(other) on B -- it rewrites the decoder's one set of input buffers, so it
+    must not run before the decode on A has read them; a pack of the texture on C.  The texture and the pack are the new
+    frame's only if the cropped decode waited for the decode, the cropped image is the other frame's, and a decode on C
+    afterwards leaves it alone.  (The window is looked at before the cropped decode is issued: an upload waits on the
+    host for the previous one's staging.)"""
+    A, B = ss.independent_pair()
+    Cs = ss.independent_of((A, B))
+    old, new, other = (ps.sized("422", 48, 32, 4, seed=s) for s in (3, 60, 85))
+    rgba_new, rgba_old = orc.ImageData(new.jpeg()).decode(), orc.ImageData(old.jpeg()).decode()
+    assert not np.array_equal(rgba_new, rgba_old)
+    pitch, total = _geometry(48, 32, ORDER_RECT, "rgba", False)
+    dec = ca.Decoder(gpu)
+    dec.decode_blocking(ca.ImageData(old.jpeg()))
+    dec.pack_tensor(torch.empty((3, 32, 48), dtype=torch.uint8, device="cuda"), dtype="u8")
+    dec.decode_cropped(ca.ImageData(other.jpeg()), Dest(total).range, ORDER_RECT, blocking=True)
+    dec.decode_blocking(ca.ImageData(old.jpeg()))
+    dst = Dest(total)
+    packed = torch.full((3, 32, 48), 7, dtype=torch.uint8, device="cuda")
+    staged_new, staged_other, staged_old = ca.ImageData(new.jpeg()), ca.ImageData(other.jpeg()), ca.ImageData(old.jpeg())
+    torch.cuda.synchronize()
+    ss.stall(A)
+    dec.enqueue(staged_new, A.cuda_stream)
+    open_ = ss.window_open(A)
+    dec.decode_cropped(staged_other, dst.range, ORDER_RECT, hip_stream=B.cuda_stream)
+    assert dec.last_kernel() == "cropped"
+    dec.pack_tensor(packed, dtype="u8", hip_stream=Cs.cuda_stream)
+    for s in (A, B, Cs):
+        s.synchronize()
+    torch.cuda.synchronize()
+    assert open_, WINDOW
+    assert np.array_equal(dec.read_texture(48, 32), rgba_new), "the decode on the first stream did not decode its own frame"
+    assert np.array_equal(packed.cpu().numpy(), _u8_pack_want(rgba_new)), "the pack on the third stream did not read the decode on the first"
+    want = _want(crs.frame_rgba(other), ORDER_RECT, "rgba", pitch, total)
+    _compare(dst.read("ordering, decoder")[0], want, "ordering, decoder: the cropped image")
+    dec.enqueue(staged_old, Cs.cuda_stream)
+    Cs.synchronize()
+    torch.cuda.synchronize()
+    assert np.array_equal(dec.read_texture(48, 32), rgba_old)
+    _compare(dst.read("ordering, decoder")[0], want, "ordering, decoder: the cropped image after the next decode")
+
+
+def ordering_decoder_decode_behind_a_stalled_cropped():
+    """stall(A); decode_cropped(other) on A; enqueue(new) on B -- the enqueue rewrites the input buffers the cropped decode
+    on A has yet to read.  The cropped image is the other frame's only if the enqueue waited; the texture is the new
+    frame's, and last_kernel names an RGBA kernel again."""
+    A, B = ss.independent_pair()
+    old, new, other = (ps.sized("422", 48, 32, 4, seed=s) for s in (3, 60, 85))
+    pitch, total = _geometry(48, 32, ORDER_RECT, "rgb_planar", False)
+    dec = ca.Decoder(gpu)
+    dec.decode_blocking(ca.ImageData(old.jpeg()))
+    rgba_kernel = dec.last_kernel()
+    dec.decode_cropped(ca.ImageData(other.jpeg()), Dest(total).range, ORDER_RECT, "rgb_planar", blocking=True)
+    dst = Dest(total)
+    staged_new, staged_other = ca.ImageData(new.jpeg()), ca.ImageData(other.jpeg())
+    torch.cuda.synchronize()
+    ss.stall(A)
+    dec.decode_cropped(staged_other, dst.range, ORDER_RECT, "rgb_planar", hip_stream=A.cuda_stream)
+    assert dec.last_kernel() == "cropped"
+    open_ = ss.window_open(A)
+    dec.enqueue(staged_new, B.cuda_stream)
+    for s in (A, B):
+        s.synchronize()
+    torch.cuda.synchronize()
+    assert open_, WINDOW
+    assert dec.last_kernel() == rgba_kernel != "cropped"
+    _compare(dst.read("ordering, decoder")[0], _want(crs.frame_rgba(other), ORDER_RECT, "rgb_planar", pitch, total), "ordering, decoder: the cropped image")
+    assert np.array_equal(dec.read_texture(48, 32), orc.ImageData(new.jpeg()).decode()), "the decode on the second stream did not decode its own frame"
+
+
+CASES = {f"cut_edges_and_intervals[{lay}]": (cut_edges_and_intervals, (lay,)) for lay in ("422", "444", "440", "420", "gray")}
+CASES.update({fn.__name__: (fn, ()) for fn in (skipped_waves_and_workgroups, undecoded_tail, tiny_frames, interval_longer_than_the_window,
+                                               coefficient_families, golden_files, identity_with_the_cards_own_rgba, batches, refusals_on_the_card,
+                                               ordering_batch_cropped_behind_a_stalled_decode, ordering_batch_decode_behind_a_stalled_cropped,
+                                               ordering_decoder_cropped_behind_a_stalled_decode, ordering_decoder_decode_behind_a_stalled_cropped)})
+
+
+def main(out_path, only=""):
+    global torch, ca, ps, crs, cs, gs, orc, ss, gpu
+    t0 = time.time()
+    import torch   # first: see the module's docstring
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for p in (root, os.path.join(root, "tests")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import compeg_amd as ca
+    import coef_stream as cs
+    import crop_stream as crs
+    import gray_stream as gs
+    import planes_stream as ps
+    import stream_stall as ss
+    from oracle import oracle as orc
+    gpu = ca.Gpu.open(0)
+    results, device_said_no = {}, False
+    for name, (fn, args) in CASES.items():
+        if only not in name:
+            continue
+        t1 = time.time()
+        try:
+            fn(*args)
+            results[name] = None
+        except ca.Error as e:
+            results[name] = f"compeg_amd.Error {e.code}: {e}\n{traceback.format_exc()}"
+            device_said_no = e.code == ca.E_HIP
+        except AssertionError:
+            results[name] = traceback.format_exc()
+        except Exception:   # (torch's own errors come from the device as well)
+            results[name] = traceback.format_exc()
+            device_said_no = True
+        print(f"{name}: {'ok' if results[name] is None else 'FAILED'} in {time.time() - t1:.2f} s", flush=True)
+        results["wall_s"] = round(time.time() - t0, 2)
+        with open(out_path, "w") as f:   # (kept current: what ran is on record whatever happens next)
+            json.dump(results, f)
+        if device_said_no:   # nothing more is started on it
+            break
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else ""))
