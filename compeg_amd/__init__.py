@@ -19,7 +19,7 @@ import numpy as np
 
 from ._lib import (CropSpec, E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
                    LIB_PATH, METADATA_BYTES, Error, FilterSpec, LumaSpec, NhwcSpec, OrientedRegion, PlanesLayout, PlanesSpec, Rect, ReducedSpec, Region, ResizeSpec,
-                   TensorSpec, check,
+                   ScaledSpec, TensorSpec, check,
                    lib)
 
 __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Texture", "Error", "HostBuffer", "JpegList",
@@ -28,15 +28,18 @@ __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Te
            "region_tensor_shape", "FILTER_KERNELS", "FilterSpec", "filtered_tensor_shape", "ORIENTATIONS", "OrientedRegion",
            "orient_rect", "oriented_tensor_shape", "NhwcSpec", "nhwc_tensor_shape", "LumaSpec", "LUMA_WEIGHTS",
            "luma_tensor_shape", "PlanesSpec", "PlanesLayout", "PLANES_FORMATS", "PLANES_CHROMA", "planes_shape",
-           "ReducedSpec", "REDUCED_FORMATS", "reduced_shape", "CropSpec", "CROP_FORMATS", "crop_shape"]
+           "ReducedSpec", "REDUCED_FORMATS", "reduced_shape", "CropSpec", "CROP_FORMATS", "crop_shape",
+           "ScaledSpec", "SCALED_FORMATS", "scaled_shape", "DECODE_KERNEL_NAMES"]
 
 
 # compeg_decoder_last_kernel / compeg_batch_last_kernel (include/compeg_hip.h: COMPEG_KERNEL_*).  KERNEL_NAMES: the RGBA
 # routes and the planes decode, ten names (tests/test_planes_stream.py pins the count); ALL_KERNEL_NAMES: every value
 # last_kernel() can give, the reduced decode's (COMPEG_KERNEL_REDUCED = 10) and the cropped decode's
-# (COMPEG_KERNEL_CROPPED = 11) behind them.
+# (COMPEG_KERNEL_CROPPED = 11) behind them, twelve names (tests/test_crop_stream.py pins the count); DECODE_KERNEL_NAMES:
+# those and the scaled decode's (COMPEG_KERNEL_SCALED = 12), what both last_kernel() methods index.
 KERNEL_NAMES = ("none", "fused", "pair", "coop_team", "generic", "split", "fused_layout", "fused_stream", "walk_mcu", "planes")
 ALL_KERNEL_NAMES = KERNEL_NAMES + ("reduced", "cropped")
+DECODE_KERNEL_NAMES = ALL_KERNEL_NAMES + ("scaled",)
 
 
 def version():
@@ -470,6 +473,32 @@ def reduced_shape(width, height, format="rgba", pitch=None):
     return ow.value, oh.value, pt.value, total.value
 
 
+# Scaled decode (include/compeg_hip.h: COMPEG_SCALED_*): formats by name
+SCALED_FORMATS = {"rgba": 0, "rgb_planar": 1}
+
+
+def _scaled_spec(denominator, format, pitch):
+    """compeg_scaled_spec from a name (or the header's number, which the library checks, as it checks the denominator);
+    pitch: None or 0 = tight."""
+    if isinstance(format, str) and format not in SCALED_FORMATS:
+        raise Error(f"unknown scaled format {format!r} (one of {', '.join(SCALED_FORMATS)})")
+    spec = ScaledSpec()
+    spec.denominator = denominator
+    spec.format = SCALED_FORMATS[format] if isinstance(format, str) else format
+    spec.pitch = int(pitch or 0)
+    return spec
+
+
+def scaled_shape(width, height, denominator, format="rgba", pitch=None):
+    """(ow, oh, pitch, total_bytes) of the decode of one width x height image at 1 / denominator (2, 4 or 8) --
+    compeg_scaled_shape; no device needed.  ow x oh = ceil(width / denominator) x ceil(height / denominator); "rgba": rows
+    of 4 ow bytes at `pitch` (a multiple of 4, None = tight); "rgb_planar": a tight [3, oh, ow] u8 block."""
+    spec = _scaled_spec(denominator, format, pitch)
+    ow, oh, pt, total = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+    check(lib.compeg_scaled_shape(C.byref(spec), width, height, C.byref(ow), C.byref(oh), C.byref(pt), C.byref(total)))
+    return ow.value, oh.value, pt.value, total.value
+
+
 # Cropped decode (include/compeg_hip.h: COMPEG_CROP_*): formats by name
 CROP_FORMATS = {"rgba": 0, "rgb_planar": 1}
 
@@ -804,6 +833,25 @@ class Decoder:
         else:
             check(lib.compeg_decoder_decode_reduced(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
 
+    def decode_scaled(self, data, dst, denominator, format="rgba", pitch=None, hip_stream=0, blocking=False):
+        """Extension (compeg_decoder_decode_scaled): uploads and preprocesses `data` as enqueue does and records, on
+        hip_stream (0 = the gpu's stream), a decode at 1 / denominator (2, 4 or 8) into caller-owned device memory as
+        scaled_shape lays it out.  Every data unit gives N x N samples, N = 8 / denominator, from the N-point inverse DCT
+        of the N x N lowest-frequency corner of its coefficients (IJG libjpeg's scaled IDCT in pinned f32 arithmetic:
+        include/compeg_hip.h, "Scaled decode"); chroma is taken to the nearest neighbour, the colour step is the full
+        decode's.  The result is neither the N x N block mean of the full decode nor libjpeg-turbo's output.
+        Denominator 8 is decode_reduced, byte for byte, and last_kernel() then says "reduced".  dst: (address, nbytes),
+        a tensor, or a __cuda_array_interface__ object of at least total_bytes.  The texture and what the packs read are
+        not touched.  Returns without waiting; blocking=True (the gpu's stream only) waits for the decode."""
+        spec = _scaled_spec(denominator, format, pitch)
+        addr, nbytes = _device_range(dst)
+        if blocking:
+            if hip_stream:
+                raise Error("decode_scaled: blocking=True records on the gpu's own stream")
+            check(lib.compeg_decoder_decode_scaled_blocking(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes))
+        else:
+            check(lib.compeg_decoder_decode_scaled(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
+
     def decode_cropped(self, data, dst, rect, format="rgba", pitch=None, hip_stream=None, blocking=False):
         """Extension (compeg_decoder_decode_cropped): uploads and preprocesses `data` as enqueue does and records, on
         hip_stream (None or 0 = the gpu's stream), a decode of rect = (x, y, w, h) -- pixels of the image, non-empty,
@@ -832,7 +880,7 @@ class Decoder:
 
     def last_kernel(self):
         """Diagnostics: the decode kernel the last enqueue went to (KERNEL_* names)."""
-        return ALL_KERNEL_NAMES[lib.compeg_decoder_last_kernel(self._h)]
+        return DECODE_KERNEL_NAMES[lib.compeg_decoder_last_kernel(self._h)]
 
     def set_device_preprocess(self, on=True):
         """Extension: preprocess scans with the device-side scan kernels instead of on the host."""
@@ -1028,6 +1076,17 @@ class Batch:
         addr, nbytes = _device_range(dst)
         check(lib.compeg_batch_decode_reduced(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
 
+    def decode_scaled(self, dst, denominator, format="rgba", pitch=None, hip_stream=0):
+        """Extension (compeg_batch_decode_scaled): records, on hip_stream (0 = the gpu's stream), a decode of the last
+        upload's images (all of one size and sampling) at 1 / denominator (2, 4 or 8) into caller-owned device memory,
+        image i at i * total_bytes of scaled_shape.  The samples are Decoder.decode_scaled's: the N-point inverse DCT of
+        each data unit's N x N lowest frequencies, N = 8 / denominator -- neither the block mean of the full decode nor
+        libjpeg-turbo's output; denominator 8 is decode_reduced.  dst: (address, nbytes), a tensor, or a
+        __cuda_array_interface__ object.  The RGBA outputs are not touched; wait() covers it."""
+        spec = _scaled_spec(denominator, format, pitch)
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_batch_decode_scaled(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
+
     def decode_cropped(self, dst, rect, format="rgba", pitch=None, hip_stream=None):
         """Extension (compeg_batch_decode_cropped): records, on hip_stream (None or 0 = the gpu's stream), a decode of
         rect = (x, y, w, h), one rectangle for all of the last upload's images (all of one size and sampling), into
@@ -1160,7 +1219,7 @@ class Batch:
 
     def last_kernel(self):
         """Diagnostics: the decode kernel the first launch of the last decode went to (KERNEL_NAMES)."""
-        return ALL_KERNEL_NAMES[lib.compeg_batch_last_kernel(self._h)]
+        return DECODE_KERNEL_NAMES[lib.compeg_batch_last_kernel(self._h)]
 
     def set_timing(self, on=True):
         """compeg_batch_set_timing: off = decodes record no timing events (they run closer together)."""

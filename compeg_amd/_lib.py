@@ -83,6 +83,11 @@ class ReducedSpec(C.Structure):
     _fields_ = [("denominator", C.c_uint32), ("format", C.c_uint32), ("pitch", C.c_uint32)]
 
 
+class ScaledSpec(C.Structure):
+    """compeg_scaled_spec (include/compeg_hip.h, "Scaled decode"): the scale's denominator (2, 4 or 8), format, RGBA pitch."""
+    _fields_ = [("denominator", C.c_uint32), ("format", C.c_uint32), ("pitch", C.c_uint32)]
+
+
 class CropSpec(C.Structure):
     """compeg_crop_spec (include/compeg_hip.h, "Cropped decode"): the rectangle in pixels of the image, format, RGBA pitch."""
     _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32),
@@ -200,6 +205,10 @@ def _load():
         "compeg_batch_decode_reduced": (i, [vp, C.POINTER(ReducedSpec), vp, sz, vp]),
         "compeg_decoder_decode_reduced": (i, [vp, vp, C.POINTER(ReducedSpec), vp, sz, vp]),
         "compeg_decoder_decode_reduced_blocking": (i, [vp, vp, C.POINTER(ReducedSpec), vp, sz]),
+        "compeg_scaled_shape": (i, [C.POINTER(ScaledSpec), u32, u32, pu32, pu32, pu32, C.POINTER(C.c_uint64)]),
+        "compeg_batch_decode_scaled": (i, [vp, C.POINTER(ScaledSpec), vp, sz, vp]),
+        "compeg_decoder_decode_scaled": (i, [vp, vp, C.POINTER(ScaledSpec), vp, sz, vp]),
+        "compeg_decoder_decode_scaled_blocking": (i, [vp, vp, C.POINTER(ScaledSpec), vp, sz]),
         "compeg_crop_shape": (i, [C.POINTER(CropSpec), u32, u32, pu32, C.POINTER(C.c_uint64)]),
         "compeg_batch_decode_cropped": (i, [vp, C.POINTER(CropSpec), vp, sz, vp]),
         "compeg_decoder_decode_cropped": (i, [vp, vp, C.POINTER(CropSpec), vp, sz, vp]),

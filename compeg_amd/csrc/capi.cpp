@@ -2153,6 +2153,149 @@ int compeg_decoder_decode_reduced_blocking(compeg_decoder *dec, const compeg_ima
 
 } // extern "C"
 
+/* ---- Scaled decode ---------------------------------------------------------- */
+
+namespace {
+
+// compeg_scaled_spec as the header has it, laid out for a width x height image: 0 with *out filled in, or the error
+// recorded.  (The texts name values, not the header's macros.)
+int scaled_layout(const compeg_scaled_spec *spec, uint32_t width, uint32_t height, ReducedLayout *out)
+{
+    if (!spec)
+        return fail(COMPEG_E_INVALID_ARG, "spec is NULL");
+    const uint32_t den = spec->denominator;
+    if (den != 2u && den != 4u && den != 8u)
+        return fail(COMPEG_E_INVALID_ARG, ("scaled spec: denominator " + std::to_string(den) + " is none of 2, 4, 8: 1/2, 1/4 and 1/8 are the scales built").c_str());
+    if (spec->format > COMPEG_SCALED_RGB_PLANAR)
+        return fail(COMPEG_E_INVALID_ARG, ("scaled spec: format " + std::to_string(spec->format) + " is neither 0 (rgba) nor 1 (rgb planar)").c_str());
+    if (width == 0 || height == 0)
+        return fail(COMPEG_E_INVALID_ARG, "scaled: the image has no pixels");
+    ReducedLayout l;
+    l.ow = (width - 1u) / den + 1u;
+    l.oh = (height - 1u) / den + 1u;
+    if (spec->format == COMPEG_SCALED_RGB_PLANAR) {
+        if (spec->pitch != 0u)
+            return fail(COMPEG_E_INVALID_ARG, ("scaled spec: pitch " + std::to_string(spec->pitch) + " with the planar format, whose rows are tight (pitch 0)").c_str());
+        l.pitch = l.ow;
+        l.total = 3ull * l.ow * l.oh;
+    } else {
+        const uint64_t row = 4ull * l.ow;
+        if (spec->pitch != 0u && (spec->pitch < row || spec->pitch % 4u != 0u))
+            return fail(COMPEG_E_INVALID_ARG, ("scaled spec: pitch " + std::to_string(spec->pitch) + " is not a multiple of 4 at or above the row's " +
+                                               std::to_string(row) + " bytes").c_str());
+        l.pitch = spec->pitch ? spec->pitch : uint32_t(row);
+        l.total = uint64_t(l.pitch) * l.oh;
+    }
+    *out = l;
+    return COMPEG_OK;
+}
+
+// The layout and the destination's checks, shared by both outputs below.
+int scaled_destination(const compeg_scaled_spec *spec, const DecodeFacts &f, void *device_dst, size_t dst_bytes, ReducedLayout *l)
+{
+    int rc = scaled_layout(spec, f.width, f.height, l);
+    if (rc == COMPEG_OK && spec->format == COMPEG_SCALED_RGBA && reinterpret_cast<uintptr_t>(device_dst) % 4u != 0u)
+        rc = fail(COMPEG_E_INVALID_ARG, "scaled: the rgba destination's address is not a multiple of 4");
+    if (rc == COMPEG_OK)
+        rc = check_destination("scaled", device_dst, dst_bytes, l->total, f.images);
+    return rc;
+}
+
+// Denominators 2 and 4: the scaled kernels.
+struct ScaledOutput {
+    using Target = ScaledTarget;
+    static constexpr const char *kPrefix = "scaled";
+    const compeg_scaled_spec *spec;
+    int target_for(const DecodeFacts &f, void *device_dst, size_t dst_bytes, ScaledTarget *target) const
+    {
+        ReducedLayout l;
+        const int rc = scaled_destination(spec, f, device_dst, dst_bytes, &l);
+        if (rc == COMPEG_OK) {
+            ScaledTarget t{};
+            t.dst = static_cast<uint8_t *>(device_dst);
+            t.image_stride = l.total;
+            t.ow = l.ow;
+            t.oh = l.oh;
+            t.pitch = l.pitch;
+            t.format = spec->format;
+            t.n = 8u / spec->denominator;
+            *target = t;
+        }
+        return rc;
+    }
+    static CallerDecode decode(const ScaledTarget &target) { return scaled_decode(target); }
+};
+
+// Denominator 8: the scaled spec's checks and words in front of the reduced decode's kernels (the formats' values are
+// the same in both specs).
+struct ScaledEighthOutput {
+    using Target = ReducedTarget;
+    static constexpr const char *kPrefix = "scaled";
+    const compeg_scaled_spec *spec;
+    int target_for(const DecodeFacts &f, void *device_dst, size_t dst_bytes, ReducedTarget *target) const
+    {
+        ReducedLayout l;
+        const int rc = scaled_destination(spec, f, device_dst, dst_bytes, &l);
+        if (rc == COMPEG_OK)
+            *target = reduced_target(compeg_reduced_spec{8u, spec->format, spec->pitch}, l, device_dst);
+        return rc;
+    }
+    static CallerDecode decode(const ReducedTarget &target) { return reduced_decode(target); }
+};
+static_assert(COMPEG_SCALED_RGBA == COMPEG_REDUCED_RGBA && COMPEG_SCALED_RGB_PLANAR == COMPEG_REDUCED_RGB_PLANAR, "one numbering of the formats");
+
+template <class Owner>
+int decode_scaled(Owner *owner, const compeg_image *img, const compeg_scaled_spec *spec, void *device_dst, size_t dst_bytes, void *hip_stream,
+                  bool blocking = false)
+{
+    if (spec && spec->denominator == 8u)
+        return decode_to_caller(owner, img, ScaledEighthOutput{spec}, device_dst, dst_bytes, hip_stream, blocking);
+    return decode_to_caller(owner, img, ScaledOutput{spec}, device_dst, dst_bytes, hip_stream, blocking);
+}
+
+} // namespace
+
+extern "C" {
+
+int compeg_scaled_shape(const compeg_scaled_spec *spec, uint32_t width, uint32_t height, uint32_t *out_width, uint32_t *out_height,
+                        uint32_t *pitch, uint64_t *total_bytes)
+{
+    return guarded([&] {
+        ReducedLayout l;
+        const int rc = scaled_layout(spec, width, height, &l);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (out_width)
+            *out_width = l.ow;
+        if (out_height)
+            *out_height = l.oh;
+        if (pitch)
+            *pitch = l.pitch;
+        if (total_bytes)
+            *total_bytes = l.total;
+        return ok();
+    });
+}
+
+int compeg_batch_decode_scaled(compeg_batch *batch, const compeg_scaled_spec *spec, void *device_dst, size_t dst_bytes, void *hip_stream)
+{
+    return decode_scaled(batch, nullptr, spec, device_dst, dst_bytes, hip_stream);
+}
+
+int compeg_decoder_decode_scaled(compeg_decoder *dec, const compeg_image *img, const compeg_scaled_spec *spec, void *device_dst,
+                                 size_t dst_bytes, void *hip_stream)
+{
+    return decode_scaled(dec, img, spec, device_dst, dst_bytes, hip_stream);
+}
+
+int compeg_decoder_decode_scaled_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_scaled_spec *spec, void *device_dst,
+                                          size_t dst_bytes)
+{
+    return decode_scaled(dec, img, spec, device_dst, dst_bytes, nullptr, true);
+}
+
+} // extern "C"
+
 /* ---- Cropped decode --------------------------------------------------------- */
 
 namespace {

@@ -11,6 +11,7 @@
 #include "planes_types.h"
 #include "reduced_types.h"
 #include "region_types.h"
+#include "scaled_types.h"
 
 namespace compeg {
 
@@ -227,6 +228,14 @@ uint32_t crop_wave_cap(uint32_t hs, uint32_t vs);
 hipError_t launch_cropped(const ImageDesc *descs, uint32_t images, uint32_t max_intervals, const HuffLdsPlan &plan, uint32_t hs, uint32_t vs,
                           const CropTarget &target, hipStream_t stream);
 
+// Scaled decode (scaled_kernels.hip, scaled_body.h): the images at 1/2 or 1/4 scale, target.n x target.n pixels per luma
+// data unit from an n-point inverse DCT of each data unit's lowest frequencies, into the caller's memory as `target` lays
+// it out; a lane per restart interval behind whole windows.  hs x vs as for launch_planes; plan: plan_huffman's with
+// fused = false and wave_cap = scaled_wave_cap for the target's n.  target: validated by the caller.
+uint32_t scaled_wave_cap(uint32_t hs, uint32_t vs, uint32_t n);
+hipError_t launch_scaled(const ImageDesc *descs, uint32_t images, uint32_t max_intervals, const HuffLdsPlan &plan, uint32_t hs, uint32_t vs,
+                         const ScaledTarget &target, hipStream_t stream);
+
 // A decode into the caller's memory, as the runtime's one road for them takes it (compeg_decoder::enqueue,
 // compeg_batch::decode_into): how to plan it, how to launch it, what to record.  A further output of this shape is a
 // further maker below, nothing in the runtime.
@@ -260,6 +269,15 @@ inline CallerDecode reduced_decode(const ReducedTarget &target)
 inline CallerDecode cropped_decode(const CropTarget &target)
 {
     return CallerDecode{&target, launch_caller_decode<CropTarget, launch_cropped>, true, crop_wave_cap, COMPEG_KERNEL_CROPPED};
+}
+
+// (fused = false as for the reduced decode; the wave cap is the one of the target's transform size)
+inline CallerDecode scaled_decode(const ScaledTarget &target)
+{
+    return CallerDecode{&target, launch_caller_decode<ScaledTarget, launch_scaled>, false,
+                        target.n == 4u ? +[](uint32_t hs, uint32_t vs) { return scaled_wave_cap(hs, vs, 4u); }
+                                       : +[](uint32_t hs, uint32_t vs) { return scaled_wave_cap(hs, vs, 2u); },
+                        COMPEG_KERNEL_SCALED};
 }
 
 #if defined(CG_AC_STAMPS)

@@ -204,6 +204,8 @@ int compeg_decoder_last_stage_times(const compeg_decoder *dec, compeg_stage_time
                                        (compeg_*_decode_reduced), a lane per restart interval */
 #define COMPEG_KERNEL_CROPPED 11     /* decode_cropped_422 / _444 / _440 / _420 / _gray_kernel: a cropped decode
                                        (compeg_*_decode_cropped), a lane per restart interval that touches the rectangle */
+#define COMPEG_KERNEL_SCALED 12      /* decode_scaled_422 / _444 / _440 / _420 / _gray_kernel: a scaled decode at 1/2 or
+                                       1/4 (compeg_*_decode_scaled), a lane per restart interval */
 int compeg_decoder_last_kernel(const compeg_decoder *dec);
 /* Extension: on != 0 moves the scan preprocessing of every following decode
  * from the host (the reference's data flow, default) to the device-side scan
@@ -943,6 +945,90 @@ int compeg_decoder_decode_cropped(compeg_decoder *dec, const compeg_image *img, 
                                   size_t dst_bytes, void *hip_stream);
 int compeg_decoder_decode_cropped_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_crop_spec *spec,
                                            void *device_dst, size_t dst_bytes);
+
+/* ---- Scaled decode (extension) ------------------------------------------------
+ * A fifth kind of decode: the image at 1/2, 1/4 or 1/8 scale, written into caller-owned device memory.  What libjpeg
+ * calls scale_denom = 2, 4, 8 and PIL draft(): the size a resize to a model input should start from, without a full-size
+ * image in between.  New entry points beside the old ones: the RGBA output, compeg_decoder_output / _read_output, and
+ * what the tensor packs see as "the last decode" are not touched by a scaled decode, compeg_*_decode_reduced stays as it
+ * is, and without these calls nothing behaves differently.
+ *
+ * Extent.  denominator den is 2, 4 or 8, N = 8 / den.  ow = ceil(W / den), oh = ceil(H / den).
+ *
+ * Samples.  Every data unit gives N x N samples, made from the N x N lowest-frequency corner of its dequantised
+ * coefficients: F[v][u] with v, u < N, v the vertical frequency, natural index v * 8 + u (zig-zag positions 24 and
+ * below: all inside what the decoder retains).  The transform is the separable N-point inverse DCT
+ *     f(x, y) = 1/4 sum_u sum_v C(u) C(v) F[v][u] cos((2x + 1) u pi / 2N) cos((2y + 1) v pi / 2N) + 128.5
+ * with C(0) = 1 / sqrt(2), C(k) = 1 otherwise, and the sample is trunc(clamp(f, 0, 255)).  This is IJG libjpeg's scaled
+ * IDCT (jidctint.c's reduced-size outputs), NOT libjpeg-turbo's jidctred, and NOT the N x N block means of the full
+ * decode: the high frequencies are dropped before the transform, not averaged away after it, and the colour step clamps
+ * per pixel.
+ *
+ * Pinned arithmetic.  f32 throughout, every step one IEEE operation, nothing contracted into a fused multiply-add.
+ *   inputs      in = float(dc) * 0.125f for the DC term (dc: the prediction-summed, dequantised DC term with 32-bit
+ *               wrap, as every other decode takes it); in = (float(level) * quant[z]) * 0.125f for an AC term at zig-zag
+ *               position z.
+ *   order       the column pass (over v, for each u) first, then the row pass (over u, for each y), which adds 128.5f to
+ *               its first input before anything else.
+ *   N = 4 pass  A = (float)1.306562965 (sqrt2 cos(pi/8)), B = (float)0.541196100 (sqrt2 cos(3 pi/8)):
+ *               e0 = in0 + in2; e1 = in0 - in2; o0 = (in1 * A) + (in3 * B); o1 = (in1 * B) - (in3 * A);
+ *               out0 = e0 + o0; out1 = e1 + o1; out2 = e1 - o1; out3 = e0 - o0.
+ *   N = 2 pass  out0 = in0 + in1; out1 = in0 - in1.
+ *   N = 1       the reduced decode's sample, trunc(clamp((float(dc) * 0.125f) + 128.5f, 0, 255)).
+ * With every AC term zero each of the N x N samples equals the reduced decode's sample bit for bit.
+ *
+ * Pixel (x, y) of the scaled image.  Y comes from the scaled luma plane at (x, y), Cb and Cr from the scaled chroma
+ * planes at (x / hs, y / vs) -- nearest neighbour, as the full decode replicates chroma (quirk Q4) -- and the colour step
+ * is the full decode's integer YCbCr -> RGB with A = 255.  For grayscale files R = G = B = s.
+ *
+ * MCUs behind the last complete restart interval are not decoded and their bytes in the destination are NOT WRITTEN:
+ * the memory is the caller's, its previous contents stay.  Nothing outside ow x oh is ever written -- not the rest of
+ * a row inside its pitch, not a row below the last; an MCU the scaled extent cuts is stored in part.
+ *
+ * format:
+ *   RGBA        interleaved R G B A, 4 bytes a pixel, A = 255.  pitch: bytes from row to row, 0 = tight (4 ow).  The
+ *               destination's address and the pitch must be multiples of 4 (COMPEG_E_INVALID_ARG otherwise).
+ *   RGB_PLANAR  [3, oh, ow] bytes, tight, any address: a CHW u8 tensor as it stands.  pitch must be 0.
+ * denominator must be 2, 4 or 8 (COMPEG_E_INVALID_ARG for any other value).  Denominator 8 runs the reduced decode's
+ * kernels: its bytes are compeg_*_decode_reduced's and the last kernel is then COMPEG_KERNEL_REDUCED. */
+#define COMPEG_SCALED_RGBA 0
+#define COMPEG_SCALED_RGB_PLANAR 1
+typedef struct compeg_scaled_spec {
+    uint32_t denominator; /* 2, 4 or 8 */
+    uint32_t format;      /* COMPEG_SCALED_* */
+    uint32_t pitch;       /* RGBA: bytes from row to row, 0 = tight; RGB_PLANAR: 0 */
+} compeg_scaled_spec;     /* 12 bytes */
+/* No device needed: the scaled extent of a width x height image, the pitch that will be used (RGB_PLANAR: ow) and one
+ * image's bytes (RGBA: pitch * oh, the last row at its full pitch; RGB_PLANAR: 3 * ow * oh).  Any output may be NULL.
+ * COMPEG_E_INVALID_ARG for: a NULL spec, a denominator other than 2, 4 or 8 (the message says which are built), a format
+ * out of range, RGB_PLANAR with a pitch, an RGBA pitch below 4 * ow or not a multiple of 4 (the message names both), a
+ * zero extent.  Nothing is written on failure. */
+int compeg_scaled_shape(const compeg_scaled_spec *spec, uint32_t width, uint32_t height, uint32_t *out_width,
+                        uint32_t *out_height, uint32_t *pitch, uint64_t *total_bytes);
+/* The images of the batch's last upload, image i to device_dst + i * total_bytes.  All images must have one size and one
+ * sampling (COMPEG_E_INVALID_ARG with a message otherwise, as compeg_batch_decode_planes asks); dst_bytes below
+ * count * total_bytes is refused before anything is launched (the message names both numbers).  Records on hip_stream
+ * (NULL = the gpu's stream) and returns without waiting; compeg_batch_wait covers it.  compeg_batch_set_chunk and the
+ * three preprocessing modes work as for compeg_batch_decode.  Any number of calls, with different specs, in any order
+ * with the batch's other decodes, after one upload.  It records none of the batch's timing events.  Ordering is the
+ * tensor packs': a scaled decode on another stream than the batch's previous work waits for that work, and what the
+ * batch does next on another stream waits for it.  compeg_batch_last_kernel then says COMPEG_KERNEL_SCALED
+ * (denominator 8: COMPEG_KERNEL_REDUCED).
+ * Known limits: a lane per restart interval on every launch (no cooperative, walk or streamed-window form: a single
+ * frame or long intervals decode slowly); no mixed sizes or samplings; no scales above 1 and no other denominators; no
+ * planes (YCbCr) output at reduced size; the tensor packs do not read a caller's image. */
+int compeg_batch_decode_scaled(compeg_batch *batch, const compeg_scaled_spec *spec, void *device_dst, size_t dst_bytes,
+                               void *hip_stream);
+/* One image: uploads and preprocesses as compeg_decoder_enqueue does (host or device preprocessing), records the
+ * scaled decode on hip_stream (NULL = the gpu's stream) and returns without waiting.  The decoder's texture, its
+ * extent and what the packs read stay those of the last RGBA decode.  To wait: synchronise hip_stream, or call
+ * compeg_decoder_decode_scaled_blocking, which does.  The decoder's next enqueue or pack on another stream waits for
+ * the scaled decode, as this call waits for the decoder's previous work.  compeg_decoder_last_kernel then says
+ * COMPEG_KERNEL_SCALED (denominator 8: COMPEG_KERNEL_REDUCED). */
+int compeg_decoder_decode_scaled(compeg_decoder *dec, const compeg_image *img, const compeg_scaled_spec *spec, void *device_dst,
+                                 size_t dst_bytes, void *hip_stream);
+int compeg_decoder_decode_scaled_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_scaled_spec *spec,
+                                          void *device_dst, size_t dst_bytes);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -140,6 +140,16 @@ pub struct compeg_reduced_spec {
     pub pitch: u32,
 }
 
+/// What a scaled decode writes (compeg_hip.h, "Scaled decode"): the scale's denominator (2, 4 or 8), the format and the
+/// RGBA row pitch in bytes (0 = tight).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct compeg_scaled_spec {
+    pub denominator: u32,
+    pub format: u32,
+    pub pitch: u32,
+}
+
 /// What a cropped decode writes (compeg_hip.h, "Cropped decode"): the rectangle in pixels of the image, the format and
 /// the RGBA row pitch in bytes (0 = tight); `reserved` is 0.
 #[repr(C)]
@@ -175,6 +185,9 @@ pub const COMPEG_KERNEL_WALK_MCU: c_int = 8;
 pub const COMPEG_KERNEL_PLANES: c_int = 9;
 pub const COMPEG_KERNEL_REDUCED: c_int = 10;
 pub const COMPEG_KERNEL_CROPPED: c_int = 11;
+pub const COMPEG_KERNEL_SCALED: c_int = 12;
+pub const COMPEG_SCALED_RGBA: u32 = 0;
+pub const COMPEG_SCALED_RGB_PLANAR: u32 = 1;
 pub const COMPEG_CROP_RGBA: u32 = 0;
 pub const COMPEG_CROP_RGB_PLANAR: u32 = 1;
 pub const COMPEG_REDUCED_RGBA: u32 = 0;
@@ -413,4 +426,12 @@ extern "C" {
                                          device_dst: *mut c_void, dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
     pub fn compeg_decoder_decode_cropped_blocking(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_crop_spec,
                                                   device_dst: *mut c_void, dst_bytes: usize) -> c_int;
+    pub fn compeg_scaled_shape(spec: *const compeg_scaled_spec, width: u32, height: u32, out_width: *mut u32, out_height: *mut u32,
+                               pitch: *mut u32, total_bytes: *mut u64) -> c_int;
+    pub fn compeg_batch_decode_scaled(batch: *mut compeg_batch, spec: *const compeg_scaled_spec, device_dst: *mut c_void,
+                                      dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_decoder_decode_scaled(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_scaled_spec,
+                                        device_dst: *mut c_void, dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_decoder_decode_scaled_blocking(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_scaled_spec,
+                                                 device_dst: *mut c_void, dst_bytes: usize) -> c_int;
 }

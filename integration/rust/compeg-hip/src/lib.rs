@@ -431,6 +431,57 @@ pub fn reduced_shape(spec: &ReducedSpec, width: u32, height: u32) -> Result<Redu
     Ok(s)
 }
 
+/// The format of a scaled decode (compeg_hip.h, "Scaled decode").
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum ScaledFormat {
+    /// Interleaved R G B A, A = 255; address and pitch multiples of 4.
+    Rgba,
+    /// `[3, oh, ow]` bytes, tight: a CHW u8 tensor.
+    RgbPlanar,
+}
+
+/// What `Decoder::decode_scaled` / `Batch::decode_scaled` write: the image at 1 / `denominator` (2, 4 or 8; the library
+/// refuses any other), N x N pixels per luma data unit, N = 8 / denominator, from the N-point inverse DCT of each data
+/// unit's N x N lowest frequencies (IJG libjpeg's scaled IDCT in pinned f32 arithmetic) -- neither the block mean of the
+/// full decode nor libjpeg-turbo's output.  Denominator 8 is the reduced decode.  `pitch`: the RGBA rows' pitch in
+/// bytes, 0 = tight.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct ScaledSpec {
+    pub denominator: u32,
+    pub format: ScaledFormat,
+    pub pitch: u32,
+}
+
+/// `scaled_shape`'s answer: the scaled extent, the pitch in use and one image's bytes.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct ScaledShape {
+    pub width: u32,
+    pub height: u32,
+    pub pitch: u32,
+    pub total_bytes: u64,
+}
+
+impl ScaledSpec {
+    pub fn new(denominator: u32, format: ScaledFormat) -> Self {
+        ScaledSpec { denominator, format, pitch: 0 }
+    }
+
+    fn raw(&self) -> ffi::compeg_scaled_spec {
+        let format = match self.format {
+            ScaledFormat::Rgba => ffi::COMPEG_SCALED_RGBA,
+            ScaledFormat::RgbPlanar => ffi::COMPEG_SCALED_RGB_PLANAR,
+        };
+        ffi::compeg_scaled_spec { denominator: self.denominator, format, pitch: self.pitch }
+    }
+}
+
+/// No device needed: the extent and size of a `width x height` image at the spec's scale.
+pub fn scaled_shape(spec: &ScaledSpec, width: u32, height: u32) -> Result<ScaledShape> {
+    let mut s = ScaledShape { width: 0, height: 0, pitch: 0, total_bytes: 0 };
+    check(unsafe { ffi::compeg_scaled_shape(&spec.raw(), width, height, &mut s.width, &mut s.height, &mut s.pitch, &mut s.total_bytes) })?;
+    Ok(s)
+}
+
 /// The format of a cropped decode (compeg_hip.h, "Cropped decode").
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum CropFormat {
@@ -899,6 +950,26 @@ impl Decoder {
         check(ffi::compeg_decoder_decode_reduced_blocking(self.raw.as_ptr(), image.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes))
     }
 
+    /// Extension: uploads and preprocesses `image` as `enqueue` does and records, on `stream`, a decode at the spec's
+    /// scale (1/2, 1/4 or 1/8) into caller-owned device memory as `scaled_shape` lays it out.  The texture and what the
+    /// packs read are not touched.  Returns without waiting: synchronise `stream`, or use `decode_scaled_blocking`.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn decode_scaled(&mut self, image: &ImageData, spec: &ScaledSpec, device_dst: *mut c_void, dst_bytes: usize,
+                                stream: Stream) -> Result<()> {
+        check(ffi::compeg_decoder_decode_scaled(self.raw.as_ptr(), image.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
+    }
+
+    /// `decode_scaled` on the gpu's own stream, and the wait for it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes.
+    pub unsafe fn decode_scaled_blocking(&mut self, image: &ImageData, spec: &ScaledSpec, device_dst: *mut c_void,
+                                         dst_bytes: usize) -> Result<()> {
+        check(ffi::compeg_decoder_decode_scaled_blocking(self.raw.as_ptr(), image.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes))
+    }
+
     /// Extension: uploads and preprocesses `image` as `enqueue` does and records, on `stream`, a decode of the spec's
     /// rectangle into caller-owned device memory as `crop_shape` lays it out; restart intervals without an MCU in the
     /// rectangle are not decoded.  The texture and what the packs read are not touched.  Returns without waiting:
@@ -1179,6 +1250,16 @@ impl Batch {
     /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
     pub unsafe fn decode_reduced(&mut self, spec: &ReducedSpec, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
         check(ffi::compeg_batch_decode_reduced(self.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
+    }
+
+    /// Extension: records a decode of the last upload's images (all of one size and sampling) at the spec's scale (1/2,
+    /// 1/4 or 1/8) into caller-owned device memory, image i at `i * total_bytes` of `scaled_shape`.  The RGBA outputs are
+    /// not touched.  Returns without waiting; `wait` covers it.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
+    pub unsafe fn decode_scaled(&mut self, spec: &ScaledSpec, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        check(ffi::compeg_batch_decode_scaled(self.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
     }
 
     /// Extension: records a decode of the spec's rectangle, one for all of the last upload's images (all of one size and
