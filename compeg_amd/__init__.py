@@ -19,7 +19,7 @@ import numpy as np
 
 from ._lib import (CropSpec, E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
                    LIB_PATH, METADATA_BYTES, Error, FilterSpec, LumaSpec, NhwcSpec, OrientedRegion, PlanesLayout, PlanesSpec, Rect, ReducedSpec, Region, ResizeSpec,
-                   ScaledSpec, TensorSpec, check,
+                   LevelsLayout, LevelsSpec, ScaledSpec, TensorSpec, check,
                    lib)
 
 __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Texture", "Error", "HostBuffer", "JpegList",
@@ -29,17 +29,20 @@ __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Te
            "orient_rect", "oriented_tensor_shape", "NhwcSpec", "nhwc_tensor_shape", "LumaSpec", "LUMA_WEIGHTS",
            "luma_tensor_shape", "PlanesSpec", "PlanesLayout", "PLANES_FORMATS", "PLANES_CHROMA", "planes_shape",
            "ReducedSpec", "REDUCED_FORMATS", "reduced_shape", "CropSpec", "CROP_FORMATS", "crop_shape",
-           "ScaledSpec", "SCALED_FORMATS", "scaled_shape", "DECODE_KERNEL_NAMES"]
+           "ScaledSpec", "SCALED_FORMATS", "scaled_shape", "DECODE_KERNEL_NAMES",
+           "LevelsSpec", "LevelsLayout", "LEVELS_ORDERS", "levels_shape", "LAST_KERNEL_NAMES"]
 
 
 # compeg_decoder_last_kernel / compeg_batch_last_kernel (include/compeg_hip.h: COMPEG_KERNEL_*).  KERNEL_NAMES: the RGBA
 # routes and the planes decode, ten names (tests/test_planes_stream.py pins the count); ALL_KERNEL_NAMES: every value
 # last_kernel() can give, the reduced decode's (COMPEG_KERNEL_REDUCED = 10) and the cropped decode's
 # (COMPEG_KERNEL_CROPPED = 11) behind them, twelve names (tests/test_crop_stream.py pins the count); DECODE_KERNEL_NAMES:
-# those and the scaled decode's (COMPEG_KERNEL_SCALED = 12), what both last_kernel() methods index.
+# those and the scaled decode's (COMPEG_KERNEL_SCALED = 12), thirteen names (tests/test_scaled_stream.py pins the count);
+# LAST_KERNEL_NAMES: those and the levels decode's (COMPEG_KERNEL_LEVELS = 13), what both last_kernel() methods index.
 KERNEL_NAMES = ("none", "fused", "pair", "coop_team", "generic", "split", "fused_layout", "fused_stream", "walk_mcu", "planes")
 ALL_KERNEL_NAMES = KERNEL_NAMES + ("reduced", "cropped")
 DECODE_KERNEL_NAMES = ALL_KERNEL_NAMES + ("scaled",)
+LAST_KERNEL_NAMES = DECODE_KERNEL_NAMES + ("levels",)
 
 
 def version():
@@ -499,6 +502,37 @@ def scaled_shape(width, height, denominator, format="rgba", pitch=None):
     return ow.value, oh.value, pt.value, total.value
 
 
+# Levels decode: quantised DCT coefficients (include/compeg_hip.h: COMPEG_LEVELS_*): orders by name
+LEVELS_ORDERS = {"zigzag": 0, "natural": 1}
+
+
+def _levels_order(order):
+    if isinstance(order, str) and order not in LEVELS_ORDERS:
+        raise Error(f"unknown levels order {order!r} (one of {', '.join(LEVELS_ORDERS)})")
+    return LEVELS_ORDERS[order] if isinstance(order, str) else order
+
+
+def _levels_spec(order):
+    """compeg_levels_spec from a name (or the header's number, which the library checks)."""
+    spec = LevelsSpec()
+    spec.order = _levels_order(order)
+    return spec
+
+
+def levels_shape(width, height, sampling=(2, 1), components=3, order="zigzag"):
+    """(components, total_bytes) of the quantised DCT coefficients (levels) of one width x height image whose luma is
+    sampled `sampling` (ImageData.sampling()) -- compeg_levels_shape; no device needed.  components: a tuple of dicts
+    offset / blocks_w / blocks_h / width_in_blocks / height_in_blocks, one per component: int16[blocks_h][blocks_w][64]
+    from `offset` bytes on, whole MCUs, of which the top-left width_in_blocks x height_in_blocks carry image samples."""
+    spec = _levels_spec(order)
+    lay = LevelsLayout()
+    check(lib.compeg_levels_shape(C.byref(spec), width, height, components, sampling[0], sampling[1], C.byref(lay)))
+    comps = tuple({"offset": lay.offset[c], "blocks_w": lay.blocks_w[c], "blocks_h": lay.blocks_h[c],
+                   "width_in_blocks": lay.width_in_blocks[c], "height_in_blocks": lay.height_in_blocks[c]}
+                  for c in range(lay.components))
+    return comps, lay.total_bytes
+
+
 # Cropped decode (include/compeg_hip.h: COMPEG_CROP_*): formats by name
 CROP_FORMATS = {"rgba": 0, "rgb_planar": 1}
 
@@ -669,6 +703,13 @@ class ImageData:
         hs, vs = C.c_uint32(), C.c_uint32()
         check(lib.compeg_image_sampling(self._h, C.byref(hs), C.byref(vs)))
         return hs.value, vs.value
+
+    def quant_table(self, component, order="zigzag"):
+        """Extension (compeg_image_quant_table): the 64 quantisation factors of component `component` as np.uint16, in
+        `order` ("zigzag" or "natural") -- what a level of decode_levels is multiplied by to give the coefficient."""
+        out = (C.c_uint16 * 64)()
+        check(lib.compeg_image_quant_table(self._h, component, out, _levels_order(order)))
+        return np.frombuffer(out, dtype=np.uint16).copy()
 
     @property
     def orientation(self):
@@ -852,6 +893,23 @@ class Decoder:
         else:
             check(lib.compeg_decoder_decode_scaled(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
 
+    def decode_levels(self, data, dst, order="zigzag", hip_stream=0, blocking=False):
+        """Extension (compeg_decoder_decode_levels): uploads and preprocesses `data` as enqueue does and records, on
+        hip_stream (0 = the gpu's stream), a decode of the file's quantised DCT coefficients (levels) into caller-owned
+        device memory as levels_shape lays it out: per component int16[blocks_h][blocks_w][64], whole MCUs, every value as
+        the entropy decode yields it (not multiplied by the quantiser; position 0 the DC predictor's low 16 bits; all 64
+        positions kept), in the file's zig-zag order or "natural" (row-major 8 x 8).  dst: (address, nbytes), a tensor, or
+        a __cuda_array_interface__ object of at least total_bytes at an address that is a multiple of 16.  The texture and
+        what the packs read are not touched.  Returns without waiting; blocking=True (the gpu's stream only) waits."""
+        spec = _levels_spec(order)
+        addr, nbytes = _device_range(dst)
+        if blocking:
+            if hip_stream:
+                raise Error("decode_levels: blocking=True records on the gpu's own stream")
+            check(lib.compeg_decoder_decode_levels_blocking(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes))
+        else:
+            check(lib.compeg_decoder_decode_levels(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
+
     def decode_cropped(self, data, dst, rect, format="rgba", pitch=None, hip_stream=None, blocking=False):
         """Extension (compeg_decoder_decode_cropped): uploads and preprocesses `data` as enqueue does and records, on
         hip_stream (None or 0 = the gpu's stream), a decode of rect = (x, y, w, h) -- pixels of the image, non-empty,
@@ -880,7 +938,7 @@ class Decoder:
 
     def last_kernel(self):
         """Diagnostics: the decode kernel the last enqueue went to (KERNEL_* names)."""
-        return DECODE_KERNEL_NAMES[lib.compeg_decoder_last_kernel(self._h)]
+        return LAST_KERNEL_NAMES[lib.compeg_decoder_last_kernel(self._h)]
 
     def set_device_preprocess(self, on=True):
         """Extension: preprocess scans with the device-side scan kernels instead of on the host."""
@@ -1205,6 +1263,22 @@ class Batch:
         check(lib.compeg_batch_pack_tensor_luma(self._h, C.byref(spec), C.byref(filter), C.byref(luma), list_, n, _luma_pad(pad), C.c_void_p(addr),
                                                 nbytes, C.c_void_p(hip_stream)))
 
+    def decode_levels(self, dst, order="zigzag", hip_stream=0):
+        """Extension (compeg_batch_decode_levels): records, on hip_stream (0 = the gpu's stream), a decode of the last
+        upload's images to their quantised DCT coefficients (levels) into caller-owned device memory, image i at
+        i * total_bytes of levels_shape.  The values are Decoder.decode_levels's.  All images must have one size and one
+        sampling; the address must be a multiple of 16.  Returns without waiting; wait() covers it."""
+        spec = _levels_spec(order)
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_batch_decode_levels(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream)))
+
+    def quant_table(self, index, component, order="zigzag"):
+        """The 64 quantisation factors (np.uint16, in `order`) of component `component` of image `index` of the last upload
+        (compeg_batch_quant_table)."""
+        out = (C.c_uint16 * 64)()
+        check(lib.compeg_batch_quant_table(self._h, index, component, out, _levels_order(order)))
+        return np.frombuffer(out, dtype=np.uint16).copy()
+
     def orientation(self, index):
         """The EXIF orientation tag (1..8) of image `index` of the last upload (compeg_batch_image_orientation)."""
         out = C.c_uint32()
@@ -1219,7 +1293,7 @@ class Batch:
 
     def last_kernel(self):
         """Diagnostics: the decode kernel the first launch of the last decode went to (KERNEL_NAMES)."""
-        return DECODE_KERNEL_NAMES[lib.compeg_batch_last_kernel(self._h)]
+        return LAST_KERNEL_NAMES[lib.compeg_batch_last_kernel(self._h)]
 
     def set_timing(self, on=True):
         """compeg_batch_set_timing: off = decodes record no timing events (they run closer together)."""

@@ -88,6 +88,18 @@ class ScaledSpec(C.Structure):
     _fields_ = [("denominator", C.c_uint32), ("format", C.c_uint32), ("pitch", C.c_uint32)]
 
 
+class LevelsSpec(C.Structure):
+    """compeg_levels_spec (include/compeg_hip.h, "Levels decode"): the order of a block's 64 values."""
+    _fields_ = [("order", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class LevelsLayout(C.Structure):
+    """compeg_levels_layout: where one image's blocks of quantised DCT coefficients (levels) lie, component by component."""
+    _fields_ = [("components", C.c_uint32), ("reserved", C.c_uint32), ("offset", C.c_uint64 * 3), ("blocks_w", C.c_uint32 * 3),
+                ("blocks_h", C.c_uint32 * 3), ("width_in_blocks", C.c_uint32 * 3), ("height_in_blocks", C.c_uint32 * 3),
+                ("total_bytes", C.c_uint64)]
+
+
 class CropSpec(C.Structure):
     """compeg_crop_spec (include/compeg_hip.h, "Cropped decode"): the rectangle in pixels of the image, format, RGBA pitch."""
     _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32),
@@ -209,6 +221,12 @@ def _load():
         "compeg_batch_decode_scaled": (i, [vp, C.POINTER(ScaledSpec), vp, sz, vp]),
         "compeg_decoder_decode_scaled": (i, [vp, vp, C.POINTER(ScaledSpec), vp, sz, vp]),
         "compeg_decoder_decode_scaled_blocking": (i, [vp, vp, C.POINTER(ScaledSpec), vp, sz]),
+        "compeg_levels_shape": (i, [C.POINTER(LevelsSpec), u32, u32, u32, u32, u32, C.POINTER(LevelsLayout)]),
+        "compeg_batch_decode_levels": (i, [vp, C.POINTER(LevelsSpec), vp, sz, vp]),
+        "compeg_decoder_decode_levels": (i, [vp, vp, C.POINTER(LevelsSpec), vp, sz, vp]),
+        "compeg_decoder_decode_levels_blocking": (i, [vp, vp, C.POINTER(LevelsSpec), vp, sz]),
+        "compeg_image_quant_table": (i, [vp, u32, C.POINTER(C.c_uint16), u32]),
+        "compeg_batch_quant_table": (i, [vp, sz, u32, C.POINTER(C.c_uint16), u32]),
         "compeg_crop_shape": (i, [C.POINTER(CropSpec), u32, u32, pu32, C.POINTER(C.c_uint64)]),
         "compeg_batch_decode_cropped": (i, [vp, C.POINTER(CropSpec), vp, sz, vp]),
         "compeg_decoder_decode_cropped": (i, [vp, vp, C.POINTER(CropSpec), vp, sz, vp]),

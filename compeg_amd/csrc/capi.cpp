@@ -2296,6 +2296,165 @@ int compeg_decoder_decode_scaled_blocking(compeg_decoder *dec, const compeg_imag
 
 } // extern "C"
 
+/* ---- Levels decode ---------------------------------------------------------- */
+
+namespace {
+
+// natural (row-major) index -> zig-zag position: the table of kernels_body.h's zigzag_of
+constexpr uint8_t kZigzagOf[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,
+                                   10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+
+// compeg_levels_spec as the header has it, laid out for a width x height image: 0 with *out filled in, or the error
+// recorded.  (The texts name values, not the header's macros.)
+int levels_layout(const compeg_levels_spec *spec, uint32_t width, uint32_t height, uint32_t components, uint32_t hs, uint32_t vs,
+                  compeg_levels_layout *out)
+{
+    if (!spec)
+        return fail(COMPEG_E_INVALID_ARG, "spec is NULL");
+    if (!out)
+        return fail(COMPEG_E_INVALID_ARG, "layout is NULL");
+    if (spec->order > COMPEG_LEVELS_NATURAL)
+        return fail(COMPEG_E_INVALID_ARG, ("levels spec: order " + std::to_string(spec->order) + " is neither 0 (zigzag) nor 1 (natural)").c_str());
+    for (int i = 0; i < 3; i++)
+        if (spec->reserved[i] != 0u)
+            return fail(COMPEG_E_INVALID_ARG, "levels spec: reserved must be 0");
+    const bool gray = components == 1;
+    if (components != 1 && components != 3)
+        return fail(COMPEG_E_INVALID_ARG, ("levels: " + std::to_string(components) + " components, an image has 1 or 3").c_str());
+    if (gray ? !(hs == 1 && vs == 1) : !((hs == 1 || hs == 2) && (vs == 1 || vs == 2)))
+        return fail(COMPEG_E_INVALID_ARG, ("levels: luma sampling " + std::to_string(hs) + "x" + std::to_string(vs) +
+                                           " is none of 2x1, 1x1, 1x2, 2x2 (1x1 for a grayscale image)").c_str());
+    if (width == 0 || height == 0)
+        return fail(COMPEG_E_INVALID_ARG, "levels: the image has no pixels");
+    compeg_levels_layout l;
+    memset(&l, 0, sizeof l);
+    l.components = components;
+    const uint32_t width_mcus = (width - 1u) / (8u * hs) + 1u, height_mcus = (height - 1u) / (8u * vs) + 1u;
+    uint64_t at = 0;
+    for (uint32_t c = 0; c < components; c++) {
+        const uint32_t hc = c == 0 ? hs : 1u, vc = c == 0 ? vs : 1u;
+        l.blocks_w[c] = width_mcus * hc;
+        l.blocks_h[c] = height_mcus * vc;
+        // (the component's extent in samples: ceil(W hs_c / hs_0) x ceil(H vs_c / vs_0))
+        const uint32_t cw = (width - 1u) / (hs / hc) + 1u, ch = (height - 1u) / (vs / vc) + 1u;
+        l.width_in_blocks[c] = (cw - 1u) / 8u + 1u;
+        l.height_in_blocks[c] = (ch - 1u) / 8u + 1u;
+        l.offset[c] = at;
+        const uint64_t blocks = uint64_t(l.blocks_w[c]) * l.blocks_h[c];
+        if (blocks > (UINT64_MAX / 4u - at) / 128u)
+            return fail(COMPEG_E_INVALID_ARG, ("levels: the blocks of a " + std::to_string(width) + "x" + std::to_string(height) +
+                                               " image overflow the layout's 64-bit byte counts").c_str());
+        at += blocks * 128u;
+    }
+    l.total_bytes = at;
+    *out = l;
+    return COMPEG_OK;
+}
+
+struct LevelsOutput {
+    using Target = LevelsTarget;
+    static constexpr const char *kPrefix = "levels";
+    const compeg_levels_spec *spec;
+    int target_for(const DecodeFacts &f, void *device_dst, size_t dst_bytes, LevelsTarget *target) const
+    {
+        compeg_levels_layout l;
+        int rc = levels_layout(spec, f.width, f.height, f.components, f.hs, f.vs, &l);
+        if (rc == COMPEG_OK && reinterpret_cast<uintptr_t>(device_dst) % 16u != 0u)
+            rc = fail(COMPEG_E_INVALID_ARG, "levels: the destination's address is not a multiple of 16");
+        if (rc == COMPEG_OK)
+            rc = check_destination(kPrefix, device_dst, dst_bytes, l.total_bytes, f.images);
+        if (rc == COMPEG_OK) {
+            LevelsTarget t{};
+            t.dst = static_cast<uint8_t *>(device_dst);
+            t.image_stride = l.total_bytes;
+            for (int c = 0; c < 3; c++) {
+                t.offset[c] = l.offset[c];
+                t.blocks_w[c] = l.blocks_w[c];
+                t.blocks_h[c] = l.blocks_h[c];
+            }
+            t.order = spec->order;
+            *target = t;
+        }
+        return rc;
+    }
+    static CallerDecode decode(const LevelsTarget &target) { return levels_decode(target); }
+};
+static_assert(COMPEG_LEVELS_ZIGZAG == kLevelsZigzag && COMPEG_LEVELS_NATURAL == kLevelsNatural, "one numbering of the orders");
+
+// 64 factors in zig-zag order -> out, in `order`
+int quant_table_out(const uint16_t *zigzag, uint32_t components, uint32_t component, uint16_t *out, uint32_t order)
+{
+    if (!out)
+        return fail(COMPEG_E_INVALID_ARG, "out is NULL");
+    if (order > COMPEG_LEVELS_NATURAL)
+        return fail(COMPEG_E_INVALID_ARG, ("quant table: order " + std::to_string(order) + " is neither 0 (zigzag) nor 1 (natural)").c_str());
+    if (component >= components)
+        return fail(COMPEG_E_INVALID_ARG, ("quant table: component " + std::to_string(component) + " of an image that has " +
+                                           std::to_string(components)).c_str());
+    for (int i = 0; i < 64; i++)
+        out[i] = zigzag[order == COMPEG_LEVELS_NATURAL ? kZigzagOf[i] : i];
+    return ok();
+}
+
+} // namespace
+
+extern "C" {
+
+int compeg_levels_shape(const compeg_levels_spec *spec, uint32_t width, uint32_t height, uint32_t components, uint32_t hsample,
+                        uint32_t vsample, compeg_levels_layout *layout)
+{
+    return guarded([&] {
+        const int rc = levels_layout(spec, width, height, components, hsample, vsample, layout);
+        return rc == COMPEG_OK ? ok() : rc;
+    });
+}
+
+int compeg_batch_decode_levels(compeg_batch *batch, const compeg_levels_spec *spec, void *device_dst, size_t dst_bytes, void *hip_stream)
+{
+    return decode_to_caller(batch, nullptr, LevelsOutput{spec}, device_dst, dst_bytes, hip_stream);
+}
+
+int compeg_decoder_decode_levels(compeg_decoder *dec, const compeg_image *img, const compeg_levels_spec *spec, void *device_dst,
+                                 size_t dst_bytes, void *hip_stream)
+{
+    return decode_to_caller(dec, img, LevelsOutput{spec}, device_dst, dst_bytes, hip_stream);
+}
+
+int compeg_decoder_decode_levels_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_levels_spec *spec, void *device_dst,
+                                          size_t dst_bytes)
+{
+    return decode_to_caller(dec, img, LevelsOutput{spec}, device_dst, dst_bytes, nullptr, true);
+}
+
+int compeg_image_quant_table(const compeg_image *img, uint32_t component, uint16_t out[64], uint32_t order)
+{
+    return guarded([&] {
+        if (!img)
+            return fail(COMPEG_E_INVALID_ARG, "img is NULL");
+        const ImageData &data = *img->data;
+        uint16_t q[64] = {0};
+        if (component < data.components)
+            for (int z = 0; z < 64; z++)
+                q[z] = uint16_t(data.metadata.qtables[data.metadata.components[component].qtable & 3][z]);
+        return quant_table_out(q, data.components, component, out, order);
+    });
+}
+
+int compeg_batch_quant_table(const compeg_batch *batch, size_t index, uint32_t component, uint16_t out[64], uint32_t order)
+{
+    return guarded([&] {
+        if (!batch)
+            return fail(COMPEG_E_INVALID_ARG, "batch is NULL");
+        if (index >= batch->count || index >= batch->quant_tables.size())
+            return fail(COMPEG_E_INVALID_ARG, ("quant table: image " + std::to_string(index) + " is beyond the batch's " +
+                                               std::to_string(batch->count) + " images").c_str());
+        const compeg_batch::QuantTables &t = batch->quant_tables[index];
+        return quant_table_out(t.q[component < 3u ? component : 0u], t.components, component, out, order);
+    });
+}
+
+} // extern "C"
+
 /* ---- Cropped decode --------------------------------------------------------- */
 
 namespace {

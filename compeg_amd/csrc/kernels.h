@@ -8,6 +8,7 @@
 #include "compeg_hip.h"
 #include "crop_types.h"
 #include "device_types.h"
+#include "levels_types.h"
 #include "planes_types.h"
 #include "reduced_types.h"
 #include "region_types.h"
@@ -27,8 +28,9 @@ DeviceLimits device_limits();
 // L2 entries; max_wave_words (largest scan span of 64 consecutive intervals)
 // sizes the per-wave scan window.
 // wave_cap: at most that many waves per workgroup (0: the kernel family's own limit)
+// slot_bytes: a lane's data-unit slot (the levels kernels keep 64 positions: kLevelsSlotBytes)
 HuffLdsPlan plan_huffman(uint32_t max_intervals, uint32_t images, uint32_t max_l2,
-                         uint32_t max_wave_words, bool fused, uint32_t wave_cap = 0);
+                         uint32_t max_wave_words, bool fused, uint32_t wave_cap = 0, uint32_t slot_bytes = kDuSlotBytes);
 // Largest word span covered by any group of 64 consecutive restart intervals.
 uint32_t max_wave_span(const uint32_t *starts, size_t nstarts, size_t nwords, uint32_t intervals,
                        uint32_t group = kWave);
@@ -247,6 +249,7 @@ struct CallerDecode {
     bool fused;                                     // plan_huffman's flag ...
     uint32_t (*wave_cap)(uint32_t hs, uint32_t vs); // ... and its wave_cap
     int kernel_id;                                  // COMPEG_KERNEL_*
+    uint32_t slot_bytes = kDuSlotBytes;             // ... and its slot_bytes
 };
 template <class Target, hipError_t (*Launch)(const ImageDesc *, uint32_t, uint32_t, const HuffLdsPlan &, uint32_t, uint32_t, const Target &, hipStream_t)>
 hipError_t launch_caller_decode(const void *target, uint32_t first, const ImageDesc *descs, uint32_t images, uint32_t max_intervals,
@@ -278,6 +281,20 @@ inline CallerDecode scaled_decode(const ScaledTarget &target)
                         target.n == 4u ? +[](uint32_t hs, uint32_t vs) { return scaled_wave_cap(hs, vs, 4u); }
                                        : +[](uint32_t hs, uint32_t vs) { return scaled_wave_cap(hs, vs, 2u); },
                         COMPEG_KERNEL_SCALED};
+}
+
+// Levels decode (levels_kernels.hip, levels_body.h): the images' quantised DCT coefficients as the entropy decode
+// yields them, all 64 positions of every data unit as int16 blocks of 128 bytes, component after component, into the
+// caller's memory as `target` lays it out; a lane per restart interval behind whole windows with slots of
+// kLevelsSlotBytes.  hs x vs as for launch_planes; plan: plan_huffman's with fused = false, wave_cap = levels_wave_cap
+// and slot_bytes = kLevelsSlotBytes.  target: validated by the caller.
+uint32_t levels_wave_cap();
+hipError_t launch_levels(const ImageDesc *descs, uint32_t images, uint32_t max_intervals, const HuffLdsPlan &plan, uint32_t hs, uint32_t vs,
+                         const LevelsTarget &target, hipStream_t stream);
+inline CallerDecode levels_decode(const LevelsTarget &target)
+{
+    return CallerDecode{&target, launch_caller_decode<LevelsTarget, launch_levels>, false,
+                        [](uint32_t, uint32_t) { return levels_wave_cap(); }, COMPEG_KERNEL_LEVELS, kLevelsSlotBytes};
 }
 
 #if defined(CG_AC_STAMPS)

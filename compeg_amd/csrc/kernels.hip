@@ -790,13 +790,13 @@ constexpr uint32_t kMaxWavesSplit = 16; // entropy_kernel: 4 per SIMD
 uint32_t fused_layout_wave_cap(uint32_t hs, uint32_t vs, bool pairs) { return hs == 2 && vs == 2 ? 8u : (hs == 1 && vs != 0 && pairs ? 4u : 12u); }
 
 HuffLdsPlan plan_huffman(uint32_t max_intervals, uint32_t images, uint32_t max_l2,
-                         uint32_t max_wave_words, bool fused, uint32_t wave_cap)
+                         uint32_t max_wave_words, bool fused, uint32_t wave_cap, uint32_t slot_bytes)
 {
     HuffLdsPlan p{};
     // everything behind L1: the L2 LUT and the two direct AC tables (at most 24 KB of LDS)
     p.l2_entries_in_lds = max_l2 < 12288u ? (max_l2 + 1u) & ~1u : 12288u;
     const uint32_t tables = (((kL1Entries + p.l2_entries_in_lds) * 2u) + 15u) & ~15u;
-    const uint32_t slots = kWave * kDuSlotBytes;
+    const uint32_t slots = kWave * slot_bytes;
 
     // Window: the largest word span of any wave's 64 intervals (the host knows
     // every start offset) plus the per-data-unit slack; waves that need more

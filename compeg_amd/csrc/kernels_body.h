@@ -181,11 +181,17 @@ struct __attribute__((may_alias, aligned(16))) SlotVec {
     uint32_t x, y, z, w;
 };
 
+// KEEP: the zig-zag positions the slot holds (kRetained: quirk Q3; 64: the levels decode, whose slot is
+// slot_bytes(64) long -- the dummy position lies behind the kept ones either way)
+constexpr int slot_bytes(int keep) { return keep * 2 + 16; }
+static_assert(slot_bytes(kRetained) == kDuSlotBytes, "the shared slot");
+
+template <int KEEP = kRetained>
 CG_DEV void zero_slot(uint8_t *slot)
 {
     SlotVec *p = reinterpret_cast<SlotVec *>(slot);
 #pragma unroll
-    for (int i = 0; i < kRetained / 8; i++)
+    for (int i = 0; i < KEEP / 8; i++)
         p[i] = SlotVec{0u, 0u, 0u, 0u};
 }
 
@@ -902,7 +908,7 @@ CG_DEV int32_t decode_dc_diff(PrefetchReader &r, const ImageDesc &d, const HuffS
 // AC coefficients of one data unit, reference-exact reader (see fast_ac for
 // the path normally taken).
 // pos0: the zig-zag position to go on from (a data unit begun in fast mode: fast_ac<true>).
-template <bool FAST>
+template <bool FAST, int KEEP = kRetained>
 CG_DEV void decode_ac_loop(PrefetchReader &r, const ImageDesc &d, const HuffShared &s,
                            uint32_t ac_off, int16_t *slot16, uint32_t pos0 = 1u)
 {
@@ -937,7 +943,7 @@ CG_DEV void decode_ac_loop(PrefetchReader &r, const ImageDesc &d, const HuffShar
         const uint32_t neg = ~uint32_t(int32_t(t) >> 31);      // all ones when that first bit is 0
         const uint32_t val = raw + (neg & ((0xffffffffu << nb) + 1u));
         const uint32_t p = pos + (sym >> 4);
-        slot16[p < uint32_t(kRetained) ? p : uint32_t(kRetained)] = int16_t(val);
+        slot16[p < uint32_t(KEEP) ? p : uint32_t(KEEP)] = int16_t(val);
         pos = sym == 0u ? 64u : p + ((sym == 0xf0u && !d.standard_entropy) ? 2u : 1u);
         done = pos >= 64u;
 
@@ -1176,7 +1182,7 @@ __device__ unsigned long long g_ac_stamps[4];
 
 // Returns the zig-zag position of the coefficient decoded last: 63 or more at the data unit's end; STREAM: less when
 // the lane's word in flight is no staged one (e.wptr at e.wlimit) -- whatever was consumed up to there was stream.
-template <bool STREAM = false>
+template <bool STREAM = false, int KEEP = kRetained>
 CG_DEV uint32_t fast_ac(EntropyState &e, const ImageDesc &d, const HuffShared &s, uint32_t ac_off,
                         uint32_t fast_base, int16_t *slot16)
 {
@@ -1195,7 +1201,7 @@ CG_DEV uint32_t fast_ac(EntropyState &e, const ImageDesc &d, const HuffShared &s
     // of the next iteration; the coefficient store of a symbol is issued one
     // iteration late (ahead of those reads in the LDS queue), so that its
     // completion is never waited for.
-    int16_t *pend_at = slot16 + kRetained; // the slot's padding
+    int16_t *pend_at = slot16 + KEEP; // the slot's padding
     int16_t pend_val = 0;
     while (at < 63u && (!STREAM || e.wptr < e.wlimit)) {
         CG_AC_STAMP(const uint64_t tw0 = __builtin_readcyclecounter();)
@@ -1238,7 +1244,7 @@ CG_DEV uint32_t fast_ac(EntropyState &e, const ImageDesc &d, const HuffShared &s
         CG_COUNT(lane_symbols);
         // EOB / ZRL store a zero at a position that is zero anyway (or at the
         // slot's padding)
-        pend_at = slot16 + umin(at, uint32_t(kRetained));
+        pend_at = slot16 + umin(at, uint32_t(KEEP));
         pend_val = int16_t(val);
     }
     lds_reads_done(ent, r.pre);
@@ -1256,7 +1262,7 @@ CG_DEV uint32_t fast_ac(EntropyState &e, const ImageDesc &d, const HuffShared &s
 // One data unit: DC difference + AC coefficients into `slot16` (zeroed by the
 // consumer); returns the dequantised DC term.  comp is wave-uniform.
 // STREAM: the wave's window in its streamed form (EntropyState); lane = the caller's.
-template <bool STREAM = false>
+template <bool STREAM = false, int KEEP = kRetained>
 CG_DEV int32_t entropy_data_unit(EntropyState &e, const ImageDesc &d, const HuffShared &s, uint32_t comp,
                                  int16_t *slot16, uint32_t lane = 0u)
 {
@@ -1272,13 +1278,13 @@ CG_DEV int32_t entropy_data_unit(EntropyState &e, const ImageDesc &d, const Huff
     }
     if (STREAM && e.fast) {
         if (fast_dc(e, d, s, dc_off, diff)) {
-            const uint32_t at = fast_ac<true>(e, d, s, ac_off, d.fast_off + d.fast_table[comp] * kFastEntries, slot16);
+            const uint32_t at = fast_ac<true, KEEP>(e, d, s, ac_off, d.fast_off + d.fast_table[comp] * kFastEntries, slot16);
             CG_COUNT(fast_dus);
             if (at < 63u) {
                 // the staged rows end inside this data unit: the reference reader takes the rest of it
                 CG_COUNT(left_window);
                 stream_leave_inside(e, d, s, lane);
-                decode_ac_loop<false>(e.r, d, s, ac_off, slot16, at + 1u);
+                decode_ac_loop<false, KEEP>(e.r, d, s, ac_off, slot16, at + 1u);
             }
             decoded = true;
         } else {
@@ -1290,11 +1296,11 @@ CG_DEV int32_t entropy_data_unit(EntropyState &e, const ImageDesc &d, const Huff
 #if CG_EXP == 3 // diagnostic build: the AC loop twice (idempotent: same coefficients, same final state)
             {
                 const EntropyState saved = e;
-                fast_ac(e, d, s, ac_off, d.fast_off + d.fast_table[comp] * kFastEntries, slot16);
+                fast_ac<false, KEEP>(e, d, s, ac_off, d.fast_off + d.fast_table[comp] * kFastEntries, slot16);
                 e = saved;
             }
 #endif
-            fast_ac(e, d, s, ac_off, d.fast_off + d.fast_table[comp] * kFastEntries, slot16);
+            fast_ac<false, KEEP>(e, d, s, ac_off, d.fast_off + d.fast_table[comp] * kFastEntries, slot16);
             decoded = true;
             CG_COUNT(fast_dus);
         } else {
@@ -1305,7 +1311,7 @@ CG_DEV int32_t entropy_data_unit(EntropyState &e, const ImageDesc &d, const Huff
     if (!decoded) {
         CG_COUNT(exact_dus);
         diff = decode_dc_diff(e.r, d, s, dc_off);
-        decode_ac_loop<false>(e.r, d, s, ac_off, slot16);
+        decode_ac_loop<false, KEEP>(e.r, d, s, ac_off, slot16);
     }
     // (values, not addresses, are selected: the state has to stay in registers)
     const int32_t p0 = e.pred0, p1 = e.pred1, p2 = e.pred2;

@@ -875,7 +875,7 @@ Status compeg_decoder::enqueue(const ImageData &img, hipStream_t stream, bool *c
     const uint32_t luma_h = md.components[0].hsample, luma_v = layout_vs(img);
     // (8-pixel MCUs in pairs: rows of 64 bytes; of an odd interval the last MCU alone.  Intervals of one MCU: the single form)
     const bool mcu_pairs = luma_h == 1 && md.restart_interval >= 2u;
-    const HuffLdsPlan plan = into ? plan_huffman(md.total_restart_intervals, 1, staged_lut_entries(img), span, into->fused, into->wave_cap(luma_h, luma_v))
+    const HuffLdsPlan plan = into ? plan_huffman(md.total_restart_intervals, 1, staged_lut_entries(img), span, into->fused, into->wave_cap(luma_h, luma_v), into->slot_bytes)
                                   : plan_huffman(md.total_restart_intervals, 1, staged_lut_entries(img), span, fused || !is_422(img),
                                                  is_422(img) ? 0u : fused_layout_wave_cap(luma_h, luma_v, mcu_pairs));
     last_span = span;
@@ -1243,9 +1243,14 @@ void compeg_batch::note_batch_properties(const ImageData *const *images, size_t 
     //   needs walk_shared (walk_state_shared, desc.cpp) on top of `uniform`.
     uniform = n > 0;
     orientations.resize(n);
+    quant_tables.resize(n);
     for (size_t i = 0; i < n; i++) {
         const ImageData &img = *images[i], &first = *images[0];
         orientations[i] = img.orientation;
+        quant_tables[i].components = img.components;
+        for (uint32_t c = 0; c < 3; c++)
+            for (int z = 0; z < 64; z++)
+                quant_tables[i].q[c][z] = c < img.components ? uint16_t(img.metadata.qtables[img.metadata.components[c].qtable & 3][z]) : uint16_t(0);
         generic_layout = generic_layout || !is_422(img);
         if (img.metadata.components[0].hsample != layout_h || layout_vs(img) != layout_v)
             layout_h = layout_v = 0; // (mixed samplings in one batch)
@@ -2342,7 +2347,7 @@ Status compeg_batch::decode_into(const CallerDecode &into, uint32_t hs, uint32_t
         CG_HIP(launch_scan(static_cast<const ScanDesc *>(scan_descs.ptr), n, max_tiles, stream));
     for (uint32_t at = 0; at < n; at += step) {
         const uint32_t m = std::min(step, n - at);
-        const HuffLdsPlan plan = plan_huffman(max_intervals, m, max_l2, max_span, into.fused, into.wave_cap(hs, vs));
+        const HuffLdsPlan plan = plan_huffman(max_intervals, m, max_l2, max_span, into.fused, into.wave_cap(hs, vs), into.slot_bytes);
         CG_HIP(into.launch(into.target, at, dd + at, m, max_intervals, plan, hs, vs, stream));
     }
     last_kernel = into.kernel_id;

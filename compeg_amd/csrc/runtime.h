@@ -312,4 +312,11 @@ struct compeg_batch {
     compeg::Status pack_tensor_luma(const compeg_tensor_spec &spec, const compeg_filter_spec &filter, const compeg_luma_spec &luma,
                                     const compeg_oriented_region *regions, size_t count, const float *pad, void *dst, hipStream_t stream);
     std::vector<uint32_t> orientations; // the EXIF orientation tag of every image of the last upload (note_batch_properties)
+    // ... and its quantisation tables: per image 3 x 64 factors in zig-zag order, component by component, and how many
+    // components it has (compeg_batch_quant_table)
+    struct QuantTables {
+        uint16_t q[3][64];
+        uint32_t components;
+    };
+    std::vector<QuantTables> quant_tables;
 };

@@ -15,7 +15,8 @@ namespace compeg {
 // The wave's window loads are issued first and the LUT copy runs under their latency; a wave past the image's last
 // interval leaves behind the barrier, lanes past it in a partly used wave stay (quad exchange, quad stores).
 // body(d, s, interval, lane): what a lane then does with its restart interval.
-template <class Body>
+// SLOT: bytes of a lane's data-unit slot (the plan's: plan_huffman's slot_bytes).
+template <int SLOT = kDuSlotBytes, class Body>
 __device__ __forceinline__ void whole_window_kernel(const ImageDesc *__restrict__ descs, uint32_t l2_in_lds, uint32_t window_words, Body body)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -25,7 +26,7 @@ __device__ __forceinline__ void whole_window_kernel(const ImageDesc *__restrict_
         return;
     uint16_t *l1 = reinterpret_cast<uint16_t *>(smem);
     uint16_t *l2 = l1 + kL1Entries;
-    const uint32_t wave_area = align16(window_words * 4u) + kWave * kDuSlotBytes;
+    const uint32_t wave_area = align16(window_words * 4u) + kWave * uint32_t(SLOT);
     uint8_t *wave_base = smem + align16((kL1Entries + l2_in_lds) * 2u);
     const uint32_t wave = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x / kWave))), lane = threadIdx.x % kWave;
     uint32_t *win = reinterpret_cast<uint32_t *>(wave_base + wave * wave_area);

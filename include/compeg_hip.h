@@ -206,6 +206,8 @@ int compeg_decoder_last_stage_times(const compeg_decoder *dec, compeg_stage_time
                                        (compeg_*_decode_cropped), a lane per restart interval that touches the rectangle */
 #define COMPEG_KERNEL_SCALED 12      /* decode_scaled_422 / _444 / _440 / _420 / _gray_kernel: a scaled decode at 1/2 or
                                        1/4 (compeg_*_decode_scaled), a lane per restart interval */
+#define COMPEG_KERNEL_LEVELS 13      /* decode_levels_422 / _444 / _440 / _420 / _gray_kernel: a levels decode
+                                       (compeg_*_decode_levels), a lane per restart interval */
 int compeg_decoder_last_kernel(const compeg_decoder *dec);
 /* Extension: on != 0 moves the scan preprocessing of every following decode
  * from the host (the reference's data flow, default) to the device-side scan
@@ -1029,6 +1031,100 @@ int compeg_decoder_decode_scaled(compeg_decoder *dec, const compeg_image *img, c
                                  size_t dst_bytes, void *hip_stream);
 int compeg_decoder_decode_scaled_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_scaled_spec *spec,
                                           void *device_dst, size_t dst_bytes);
+
+/* ---- Levels decode: quantised DCT coefficients (extension) ----------------------
+ * A sixth kind of decode: the file's own quantised DCT coefficients (levels), written into caller-owned device memory
+ * as int16 blocks with nothing of the transform applied -- what libjpeg calls jpeg_read_coefficients.  For DCT-domain
+ * models, transcoders and forensic tools.  New entry points beside the old ones: the RGBA output, compeg_decoder_output
+ * / _read_output, last_w / last_h and what the tensor packs see as "the last decode" are not touched by a levels decode,
+ * compeg_decoder_read_coefficients (the debug read-back of 32 dequantised positions) stays as it is, and without these
+ * calls nothing behaves differently.
+ *
+ * Layout.  Component c of a W x H image has blocks_w[c] = width_mcus * hs_c and blocks_h[c] = height_mcus * vs_c blocks
+ * (hs_c x vs_c: the component's sampling factors; chroma 1 x 1; width_mcus = ceil(W / (8 hs_0)), height_mcus =
+ * ceil(H / (8 vs_0))): whole MCUs, so every decoded data unit has a home and nothing is masked at the image's edge.  The
+ * destination holds, component after component, int16[blocks_h[c]][blocks_w[c]][64], tight; component 0 at offset 0;
+ * a grayscale image has one component.  The block of data unit (h, v) of component c in MCU (mx, my) is at
+ * offset[c] + ((by * blocks_w[c] + bx) * 64) * 2 bytes with bx = mx * hs_c + h, by = my * vs_c + v.  Image i of a batch
+ * is at i * total_bytes.  width_in_blocks[c] = ceil(comp_w / 8) and height_in_blocks[c] = ceil(comp_h / 8) with comp_w =
+ * ceil(W * hs_c / hs_0), comp_h = ceil(H * vs_c / vs_0) are libjpeg's counts of the blocks that carry image samples:
+ * the top-left width_in_blocks x height_in_blocks corner of each raster.
+ *
+ * Values.  Each value is the level as the entropy decode yields it, NOT multiplied by the quantiser.
+ *   position 0      the component's DC predictor after this unit's difference.  The predictor is a 32-bit integer that
+ *                   wraps, as on every decode route; its LOW 16 BITS are stored (two's complement).  A conforming file
+ *                   keeps it inside 16 bits; a hostile one (DC categories above 11, long runs of large differences) does
+ *                   not, and then only the low half is seen here.
+ *   positions 1..63 int16(val) of the decoded value, as the decoder's coefficient slot holds it on every route.
+ * Quirks Q1 (the reference's reader underflow) and Q2 (a ZRL advances 17 positions), COMPEG_PARSE_STANDARD_ENTROPY and
+ * DC categories above 15 act as on every other route.  Quirk Q3 does NOT act: positions 32..63 are kept.  A position
+ * beyond 63 -- a corrupt stream reaches one, and so does Q2's 17-step ZRL -- is dropped.
+ *
+ * order:
+ *   ZIGZAG   the file's order: index z of a block is zig-zag position z.
+ *   NATURAL  row-major 8 x 8 with the horizontal frequency fastest (libjpeg's JBLOCK): index v * 8 + u holds zig-zag
+ *            position ZIGZAG[v * 8 + u], the table every JPEG text prints (0 1 5 6 14 15 27 28 / 2 4 7 13 ...).
+ *
+ * MCUs behind the last complete restart interval are not decoded and their bytes in the destination are NOT WRITTEN:
+ * the memory is the caller's, its previous contents stay.  Nothing outside total_bytes per image is ever written.  The
+ * destination's address must be a multiple of 16 (every block is then a 128-byte line); a misaligned address and a
+ * dst_bytes too small are refused with COMPEG_E_INVALID_ARG and a message before anything is launched.
+ *
+ * Not built: dequantised or float output (compeg_image_quant_table gives the factors: one broadcast multiply);
+ * batches of mixed size or sampling; the cooperative, walk and streamed-window routes; tensor packs reading a caller's
+ * blocks. */
+#define COMPEG_LEVELS_ZIGZAG 0
+#define COMPEG_LEVELS_NATURAL 1
+typedef struct compeg_levels_spec {
+    uint32_t order;       /* COMPEG_LEVELS_* */
+    uint32_t reserved[3]; /* 0 */
+} compeg_levels_spec;     /* 16 bytes */
+typedef struct compeg_levels_layout {
+    uint32_t components;          /* 1 or 3 */
+    uint32_t reserved;            /* written as 0 */
+    uint64_t offset[3];           /* per component: its first byte (a multiple of 128) ... */
+    uint32_t blocks_w[3];         /* ... blocks a row of its raster ... */
+    uint32_t blocks_h[3];         /* ... and rows of blocks: whole MCUs ... */
+    uint32_t width_in_blocks[3];  /* ... of which ceil(comp_w / 8) ... */
+    uint32_t height_in_blocks[3]; /* ... by ceil(comp_h / 8) carry samples of the image; unused components are all zero */
+    uint64_t total_bytes;         /* one image's blocks */
+} compeg_levels_layout;           /* 88 bytes */
+/* No device needed: one image's layout for a width x height image of `components` components (3, or 1: grayscale)
+ * whose luma is sampled hsample x vsample (compeg_image_sampling).  COMPEG_E_INVALID_ARG for: NULL arguments, an order
+ * out of range, nonzero reserved words, a zero extent, a sampling that is none of the five, an extent whose blocks
+ * overflow the layout's 64-bit byte counts (far beyond what a JPEG header can state).  Nothing is written on failure. */
+int compeg_levels_shape(const compeg_levels_spec *spec, uint32_t width, uint32_t height, uint32_t components, uint32_t hsample,
+                        uint32_t vsample, compeg_levels_layout *layout);
+/* The images of the batch's last upload, image i to device_dst + i * total_bytes.  All images must have one size and one
+ * sampling (COMPEG_E_INVALID_ARG with a message otherwise, as compeg_batch_decode_planes asks); dst_bytes below
+ * count * total_bytes and an address that is no multiple of 16 are refused before anything is launched.  Records on
+ * hip_stream (NULL = the gpu's stream) and returns without waiting; compeg_batch_wait covers it.  compeg_batch_set_chunk
+ * and the three preprocessing modes work as for compeg_batch_decode.  Any number of calls, with different specs, in any
+ * order with the batch's other decodes, after one upload.  It records none of the batch's timing events.  Ordering is
+ * the tensor packs': a levels decode on another stream than the batch's previous work waits for that work, and what the
+ * batch does next on another stream waits for it.  compeg_batch_last_kernel then says COMPEG_KERNEL_LEVELS.
+ * Known limits: a lane per restart interval on every launch (no cooperative, walk or streamed-window form: a single
+ * frame or long intervals decode slowly); no mixed sizes or samplings; no dequantised or float output; the tensor packs
+ * do not read a caller's blocks. */
+int compeg_batch_decode_levels(compeg_batch *batch, const compeg_levels_spec *spec, void *device_dst, size_t dst_bytes,
+                               void *hip_stream);
+/* One image: uploads and preprocesses as compeg_decoder_enqueue does (host or device preprocessing), records the
+ * levels decode on hip_stream (NULL = the gpu's stream) and returns without waiting.  The decoder's texture, its
+ * extent and what the packs read stay those of the last RGBA decode.  To wait: synchronise hip_stream, or call
+ * compeg_decoder_decode_levels_blocking, which does.  The decoder's next enqueue or pack on another stream waits for
+ * the levels decode, as this call waits for the decoder's previous work.  compeg_decoder_last_kernel then says
+ * COMPEG_KERNEL_LEVELS. */
+int compeg_decoder_decode_levels(compeg_decoder *dec, const compeg_image *img, const compeg_levels_spec *spec, void *device_dst,
+                                 size_t dst_bytes, void *hip_stream);
+int compeg_decoder_decode_levels_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_levels_spec *spec,
+                                          void *device_dst, size_t dst_bytes);
+/* The quantisation table of component `component` (0 .. components - 1) of a parsed image, 64 factors in `order`
+ * (COMPEG_LEVELS_*): level * factor, position by position, is the dequantised coefficient -- no second parse of the
+ * file.  COMPEG_E_INVALID_ARG for NULL arguments, a component the image does not have, an order out of range.
+ * compeg_batch_quant_table: the same for image `index` of the batch's last upload (batches take JPEG bytes without a
+ * compeg_image). */
+int compeg_image_quant_table(const compeg_image *img, uint32_t component, uint16_t out[64], uint32_t order);
+int compeg_batch_quant_table(const compeg_batch *batch, size_t index, uint32_t component, uint16_t out[64], uint32_t order);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

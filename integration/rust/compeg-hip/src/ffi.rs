@@ -150,6 +150,29 @@ pub struct compeg_scaled_spec {
     pub pitch: u32,
 }
 
+/// What a levels decode writes (compeg_hip.h, "Levels decode"): the order of a block's 64 values; `reserved` is 0.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct compeg_levels_spec {
+    pub order: u32,
+    pub reserved: [u32; 3],
+}
+
+/// Where one image's blocks of quantised DCT coefficients lie (`compeg_levels_shape`): per component the offset, the
+/// raster of blocks (whole MCUs) and libjpeg's `width_in_blocks` / `height_in_blocks`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct compeg_levels_layout {
+    pub components: u32,
+    pub reserved: u32,
+    pub offset: [u64; 3],
+    pub blocks_w: [u32; 3],
+    pub blocks_h: [u32; 3],
+    pub width_in_blocks: [u32; 3],
+    pub height_in_blocks: [u32; 3],
+    pub total_bytes: u64,
+}
+
 /// What a cropped decode writes (compeg_hip.h, "Cropped decode"): the rectangle in pixels of the image, the format and
 /// the RGBA row pitch in bytes (0 = tight); `reserved` is 0.
 #[repr(C)]
@@ -186,6 +209,9 @@ pub const COMPEG_KERNEL_PLANES: c_int = 9;
 pub const COMPEG_KERNEL_REDUCED: c_int = 10;
 pub const COMPEG_KERNEL_CROPPED: c_int = 11;
 pub const COMPEG_KERNEL_SCALED: c_int = 12;
+pub const COMPEG_KERNEL_LEVELS: c_int = 13;
+pub const COMPEG_LEVELS_ZIGZAG: u32 = 0;
+pub const COMPEG_LEVELS_NATURAL: u32 = 1;
 pub const COMPEG_SCALED_RGBA: u32 = 0;
 pub const COMPEG_SCALED_RGB_PLANAR: u32 = 1;
 pub const COMPEG_CROP_RGBA: u32 = 0;
@@ -434,4 +460,14 @@ extern "C" {
                                         device_dst: *mut c_void, dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
     pub fn compeg_decoder_decode_scaled_blocking(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_scaled_spec,
                                                  device_dst: *mut c_void, dst_bytes: usize) -> c_int;
+    pub fn compeg_levels_shape(spec: *const compeg_levels_spec, width: u32, height: u32, components: u32, hsample: u32, vsample: u32,
+                               layout: *mut compeg_levels_layout) -> c_int;
+    pub fn compeg_batch_decode_levels(batch: *mut compeg_batch, spec: *const compeg_levels_spec, device_dst: *mut c_void,
+                                      dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_decoder_decode_levels(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_levels_spec,
+                                        device_dst: *mut c_void, dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_decoder_decode_levels_blocking(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_levels_spec,
+                                                 device_dst: *mut c_void, dst_bytes: usize) -> c_int;
+    pub fn compeg_image_quant_table(img: *const compeg_image, component: u32, out: *mut u16, order: u32) -> c_int;
+    pub fn compeg_batch_quant_table(batch: *const compeg_batch, index: usize, component: u32, out: *mut u16, order: u32) -> c_int;
 }

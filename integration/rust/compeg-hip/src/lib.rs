@@ -482,6 +482,50 @@ pub fn scaled_shape(spec: &ScaledSpec, width: u32, height: u32) -> Result<Scaled
     Ok(s)
 }
 
+/// The order of a block's 64 values in a levels decode (compeg_hip.h, "Levels decode").
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum LevelsOrder {
+    /// The file's zig-zag order.
+    Zigzag,
+    /// Row-major 8 x 8, the horizontal frequency fastest (libjpeg's `JBLOCK`).
+    Natural,
+}
+
+impl LevelsOrder {
+    fn raw(self) -> u32 {
+        match self {
+            LevelsOrder::Zigzag => ffi::COMPEG_LEVELS_ZIGZAG,
+            LevelsOrder::Natural => ffi::COMPEG_LEVELS_NATURAL,
+        }
+    }
+}
+
+/// What `Decoder::decode_levels` / `Batch::decode_levels` write: the file's quantised DCT coefficients (levels) as
+/// `i16` blocks of 64, per component `[blocks_h][blocks_w][64]`, whole MCUs -- every value as the entropy decode yields it
+/// (not multiplied by the quantiser; position 0 the DC predictor's low 16 bits; all 64 positions kept).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct LevelsSpec {
+    pub order: LevelsOrder,
+}
+
+impl LevelsSpec {
+    pub fn new(order: LevelsOrder) -> Self {
+        LevelsSpec { order }
+    }
+
+    fn raw(&self) -> ffi::compeg_levels_spec {
+        ffi::compeg_levels_spec { order: self.order.raw(), reserved: [0; 3] }
+    }
+}
+
+/// No device needed: where the blocks of a `width x height` image of `components` components (3, or 1: grayscale)
+/// whose luma is sampled `sampling` (`ImageData::sampling`) lie, and how many bytes one image takes.
+pub fn levels_shape(spec: &LevelsSpec, width: u32, height: u32, components: u32, sampling: (u32, u32)) -> Result<ffi::compeg_levels_layout> {
+    let mut layout = ffi::compeg_levels_layout::default();
+    check(unsafe { ffi::compeg_levels_shape(&spec.raw(), width, height, components, sampling.0, sampling.1, &mut layout) })?;
+    Ok(layout)
+}
+
 /// The format of a cropped decode (compeg_hip.h, "Cropped decode").
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum CropFormat {
@@ -690,6 +734,14 @@ impl<'a> ImageData<'a> {
         let (mut h, mut v) = (0, 0);
         unsafe { ffi::compeg_image_sampling(self.raw.as_ptr(), &mut h, &mut v) };
         (h, v)
+    }
+
+    /// Extension: the 64 quantisation factors of component `component` in `order` -- what a level of `decode_levels` is
+    /// multiplied by to give the coefficient.
+    pub fn quant_table(&self, component: u32, order: LevelsOrder) -> Result<[u16; 64]> {
+        let mut q = [0u16; 64];
+        check(unsafe { ffi::compeg_image_quant_table(self.raw.as_ptr(), component, q.as_mut_ptr(), order.raw()) })?;
+        Ok(q)
     }
 
     /// Extension: the file's EXIF orientation tag, 1..8; 1 where it has no usable one.
@@ -959,6 +1011,27 @@ impl Decoder {
     pub unsafe fn decode_scaled(&mut self, image: &ImageData, spec: &ScaledSpec, device_dst: *mut c_void, dst_bytes: usize,
                                 stream: Stream) -> Result<()> {
         check(ffi::compeg_decoder_decode_scaled(self.raw.as_ptr(), image.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
+    }
+
+    /// Extension: uploads and preprocesses `image` as `enqueue` does and records on `stream` a decode of its quantised DCT
+    /// coefficients (levels) into caller-owned device memory as `levels_shape` lays it out.  The texture and what the
+    /// packs read are not touched.  Returns without waiting: synchronise `stream`, or use `decode_levels_blocking`.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes, at an address that is a multiple of 16, that stays
+    /// valid until the stream has run.
+    pub unsafe fn decode_levels(&mut self, image: &ImageData, spec: &LevelsSpec, device_dst: *mut c_void, dst_bytes: usize,
+                                stream: Stream) -> Result<()> {
+        check(ffi::compeg_decoder_decode_levels(self.raw.as_ptr(), image.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
+    }
+
+    /// `decode_levels` on the gpu's own stream, and the wait for it.
+    ///
+    /// # Safety
+    /// As for `decode_levels`.
+    pub unsafe fn decode_levels_blocking(&mut self, image: &ImageData, spec: &LevelsSpec, device_dst: *mut c_void,
+                                         dst_bytes: usize) -> Result<()> {
+        check(ffi::compeg_decoder_decode_levels_blocking(self.raw.as_ptr(), image.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes))
     }
 
     /// `decode_scaled` on the gpu's own stream, and the wait for it.
@@ -1270,6 +1343,23 @@ impl Batch {
     /// `device_dst` must be device memory of at least `dst_bytes` bytes that stays valid until the stream has run.
     pub unsafe fn decode_cropped(&mut self, spec: &CropSpec, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
         check(ffi::compeg_batch_decode_cropped(self.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
+    }
+
+    /// Records on `stream` a decode of the last upload's images to their quantised DCT coefficients (levels) into
+    /// caller-owned device memory, image i at `i * total_bytes` of `levels_shape`.  The RGBA outputs are not touched.
+    ///
+    /// # Safety
+    /// `device_dst` must be device memory of at least `dst_bytes` bytes, at an address that is a multiple of 16, that stays
+    /// valid until the stream has run.
+    pub unsafe fn decode_levels(&mut self, spec: &LevelsSpec, device_dst: *mut c_void, dst_bytes: usize, stream: Stream) -> Result<()> {
+        check(ffi::compeg_batch_decode_levels(self.raw.as_ptr(), &spec.raw(), device_dst, dst_bytes, stream.0))
+    }
+
+    /// The 64 quantisation factors, in `order`, of component `component` of image `index` of the last upload.
+    pub fn quant_table(&self, index: usize, component: u32, order: LevelsOrder) -> Result<[u16; 64]> {
+        let mut q = [0u16; 64];
+        check(unsafe { ffi::compeg_batch_quant_table(self.raw.as_ptr(), index, component, q.as_mut_ptr(), order.raw()) })?;
+        Ok(q)
     }
 
     /// The EXIF orientation tag (1..8) of image `index` of the last upload.
