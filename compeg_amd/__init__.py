@@ -17,7 +17,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (CropSpec, E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
+from ._lib import (CropRegion, CropRegionsSpec, CropSpec, E_COUNT_MISMATCH, E_HIP, E_INVALID_ARG, E_MALFORMED, E_UNSUPPORTED, L1_BYTES,
                    LIB_PATH, METADATA_BYTES, Error, FilterSpec, LumaSpec, NhwcSpec, OrientedRegion, PlanesLayout, PlanesSpec, Rect, ReducedSpec, Region, ResizeSpec,
                    LevelsLayout, LevelsSpec, ScaledSpec, TensorSpec, check,
                    lib)
@@ -30,7 +30,8 @@ __all__ = ["Gpu", "Decoder", "DecodeOp", "ImageData", "ScanBuffer", "Batch", "Te
            "luma_tensor_shape", "PlanesSpec", "PlanesLayout", "PLANES_FORMATS", "PLANES_CHROMA", "planes_shape",
            "ReducedSpec", "REDUCED_FORMATS", "reduced_shape", "CropSpec", "CROP_FORMATS", "crop_shape",
            "ScaledSpec", "SCALED_FORMATS", "scaled_shape", "DECODE_KERNEL_NAMES",
-           "LevelsSpec", "LevelsLayout", "LEVELS_ORDERS", "levels_shape", "LAST_KERNEL_NAMES"]
+           "LevelsSpec", "LevelsLayout", "LEVELS_ORDERS", "levels_shape", "LAST_KERNEL_NAMES",
+           "CropRegion", "CropRegionsSpec", "crop_regions_shape"]
 
 
 # compeg_decoder_last_kernel / compeg_batch_last_kernel (include/compeg_hip.h: COMPEG_KERNEL_*).  KERNEL_NAMES: the RGBA
@@ -559,6 +560,51 @@ def crop_shape(width, height, rect, format="rgba", pitch=None):
     return pt.value, total.value
 
 
+def _crop_region(region):
+    """compeg_crop_region from (image, (x, y, w, h)), (image, (x, y, w, h), (dst_x, dst_y)) or a CropRegion as it is."""
+    if isinstance(region, CropRegion):
+        return region
+    if not isinstance(region, (tuple, list)) or len(region) not in (2, 3) or len(region[1]) != 4 or (len(region) == 3 and len(region[2]) != 2):
+        raise Error(f"crop regions: {region!r} is neither (image, (x, y, w, h)), (image, (x, y, w, h), (dst_x, dst_y)) nor a CropRegion")
+    r = CropRegion()
+    r.image = int(region[0])
+    r.x, r.y, r.width, r.height = (int(v) for v in region[1])
+    r.dst_x, r.dst_y = (int(v) for v in region[2]) if len(region) == 3 else (0, 0)
+    r.reserved = 0
+    return r
+
+
+def _crop_regions_spec(slot, format, pitch):
+    """compeg_crop_regions_spec from the slot (width, height) in pixels and a format's name (or the header's number, which
+    the library checks); pitch: None or 0 = tight."""
+    if isinstance(format, str) and format not in CROP_FORMATS:
+        raise Error(f"unknown crop format {format!r} (one of {', '.join(CROP_FORMATS)})")
+    spec = CropRegionsSpec()
+    spec.slot_width, spec.slot_height = (int(v) for v in slot)
+    spec.format = CROP_FORMATS[format] if isinstance(format, str) else format
+    spec.pitch = int(pitch or 0)
+    return spec
+
+
+def _crop_regions_args(regions, slot, format, pitch):
+    """(spec, array of CropRegion, count) of a region list; slot None: the largest dst_x + w and dst_y + h of the list."""
+    items = [_crop_region(r) for r in regions]
+    if slot is None:
+        slot = (max(r.dst_x + r.width for r in items), max(r.dst_y + r.height for r in items)) if items else (1, 1)  # (no region: nothing is written)
+    array = (CropRegion * max(len(items), 1))(*items)
+    return _crop_regions_spec(slot, format, pitch), array, len(items)
+
+
+def crop_regions_shape(slot, format="rgba", pitch=None):
+    """(pitch, slot_bytes) of the cropped decode of a region list into slots of slot = (width, height) pixels --
+    compeg_crop_regions_shape; no device needed.  "rgba": slot rows of 4 width bytes at `pitch` (a multiple of 4, None =
+    tight); "rgb_planar": a tight [3, height, width] u8 block a slot.  Region k's slot lies at k * slot_bytes."""
+    spec = _crop_regions_spec(slot, format, pitch)
+    pt, total = C.c_uint32(), C.c_uint64()
+    check(lib.compeg_crop_regions_shape(C.byref(spec), C.byref(pt), C.byref(total)))
+    return pt.value, total.value
+
+
 def _host_view(data):
     a = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
     return np.ascontiguousarray(a)
@@ -926,6 +972,23 @@ class Decoder:
         else:
             check(lib.compeg_decoder_decode_cropped(self._h, data._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream or None)))
 
+    def decode_cropped_regions(self, data, dst, regions, slot=None, format="rgba", pitch=None, hip_stream=None, blocking=False):
+        """Extension (compeg_decoder_decode_cropped_regions): decode_cropped with a list of rectangles of the one image --
+        regions: (0, (x, y, w, h)), (0, (x, y, w, h), (dst_x, dst_y)) or CropRegions -- region k into slot k of dst, a
+        [len(regions), slot_h, slot_w, 4] ("rgba") or [len(regions), 3, slot_h, slot_w] ("rgb_planar") u8 block as
+        crop_regions_shape lays it out; slot=None: the largest dst_x + w and dst_y + h of the list.  What lies outside a
+        region's rectangle in its slot is not written.  Returns without waiting; blocking=True (the gpu's stream only)
+        waits for the decode."""
+        spec, array, count = _crop_regions_args(regions, slot, format, pitch)
+        addr, nbytes = _device_range(dst)
+        if blocking:
+            if hip_stream:
+                raise Error("decode_cropped_regions: blocking=True records on the gpu's own stream")
+            check(lib.compeg_decoder_decode_cropped_regions_blocking(self._h, data._h, C.byref(spec), array, count, C.c_void_p(addr), nbytes))
+        else:
+            check(lib.compeg_decoder_decode_cropped_regions(self._h, data._h, C.byref(spec), array, count, C.c_void_p(addr), nbytes,
+                                                            C.c_void_p(hip_stream or None)))
+
     def last_warning(self):
         return lib.compeg_decoder_last_warning(self._h).decode()
 
@@ -1153,6 +1216,18 @@ class Batch:
         spec = _crop_spec(rect, format, pitch)
         addr, nbytes = _device_range(dst)
         check(lib.compeg_batch_decode_cropped(self._h, C.byref(spec), C.c_void_p(addr), nbytes, C.c_void_p(hip_stream or None)))
+
+    def decode_cropped_regions(self, dst, regions, slot=None, format="rgba", pitch=None, hip_stream=None):
+        """Extension (compeg_batch_decode_cropped_regions): records, on hip_stream (None or 0 = the gpu's stream), a
+        cropped decode of a region list -- regions: (image, (x, y, w, h)), (image, (x, y, w, h), (dst_x, dst_y)) or
+        CropRegions, image an index into the last upload -- region k into slot k of dst, a [len(regions), slot_h, slot_w,
+        4] ("rgba") or [len(regions), 3, slot_h, slot_w] ("rgb_planar") u8 block as crop_regions_shape lays it out;
+        slot=None: the largest dst_x + w and dst_y + h of the list.  The images may be of any mix of sizes and samplings;
+        set_chunk bounds the regions per launch.  What lies outside a region's rectangle in its slot is not written.
+        The RGBA outputs are not touched; wait() covers it."""
+        spec, array, count = _crop_regions_args(regions, slot, format, pitch)
+        addr, nbytes = _device_range(dst)
+        check(lib.compeg_batch_decode_cropped_regions(self._h, C.byref(spec), array, count, C.c_void_p(addr), nbytes, C.c_void_p(hip_stream or None)))
 
     def wait(self):
         check(lib.compeg_batch_wait(self._h))

@@ -106,6 +106,19 @@ class CropSpec(C.Structure):
                 ("pitch", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class CropRegion(C.Structure):
+    """compeg_crop_region (include/compeg_hip.h, "Cropped decode of a region list"): which rectangle of which image lies
+    where in its slot."""
+    _fields_ = [("image", C.c_uint32), ("x", C.c_uint32), ("y", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("dst_x", C.c_uint32), ("dst_y", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CropRegionsSpec(C.Structure):
+    """compeg_crop_regions_spec: every region's slot in pixels, the format and the RGBA pitch."""
+    _fields_ = [("slot_width", C.c_uint32), ("slot_height", C.c_uint32), ("format", C.c_uint32), ("pitch", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -231,6 +244,11 @@ def _load():
         "compeg_batch_decode_cropped": (i, [vp, C.POINTER(CropSpec), vp, sz, vp]),
         "compeg_decoder_decode_cropped": (i, [vp, vp, C.POINTER(CropSpec), vp, sz, vp]),
         "compeg_decoder_decode_cropped_blocking": (i, [vp, vp, C.POINTER(CropSpec), vp, sz]),
+        "compeg_crop_regions_shape": (i, [C.POINTER(CropRegionsSpec), pu32, C.POINTER(C.c_uint64)]),
+        "compeg_crop_region_check": (i, [C.POINTER(CropRegionsSpec), u32, u32, C.POINTER(CropRegion)]),
+        "compeg_batch_decode_cropped_regions": (i, [vp, C.POINTER(CropRegionsSpec), C.POINTER(CropRegion), sz, vp, sz, vp]),
+        "compeg_decoder_decode_cropped_regions": (i, [vp, vp, C.POINTER(CropRegionsSpec), C.POINTER(CropRegion), sz, vp, sz, vp]),
+        "compeg_decoder_decode_cropped_regions_blocking": (i, [vp, vp, C.POINTER(CropRegionsSpec), C.POINTER(CropRegion), sz, vp, sz]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("COMPEG_LIB") and not hasattr(L, name):

@@ -2580,3 +2580,216 @@ int compeg_decoder_decode_cropped_blocking(compeg_decoder *dec, const compeg_ima
 }
 
 } // extern "C"
+
+/* ---- Cropped decode of a region list ------------------------------------------ */
+
+namespace {
+
+struct CropSlotLayout {
+    uint32_t pitch;
+    uint64_t slot_bytes;
+};
+
+// compeg_crop_regions_spec as the header has it: 0 with *out filled in, or the error recorded.
+int crop_regions_layout(const compeg_crop_regions_spec *spec, CropSlotLayout *out)
+{
+    if (!spec)
+        return fail(COMPEG_E_INVALID_ARG, "spec is NULL");
+    if (spec->format > COMPEG_CROP_RGB_PLANAR)
+        return fail(COMPEG_E_INVALID_ARG, ("crop regions spec: format " + std::to_string(spec->format) + " is neither 0 (rgba) nor 1 (rgb planar)").c_str());
+    for (int i = 0; i < 4; i++)
+        if (spec->reserved[i] != 0u)
+            return fail(COMPEG_E_INVALID_ARG, ("crop regions spec: reserved[" + std::to_string(i) + "] is " + std::to_string(spec->reserved[i]) +
+                                               ", it must be 0").c_str());
+    const std::string slot = std::to_string(spec->slot_width) + "x" + std::to_string(spec->slot_height);
+    if (spec->slot_width == 0 || spec->slot_height == 0)
+        return fail(COMPEG_E_INVALID_ARG, ("crop regions spec: the slot " + slot + " has no pixels").c_str());
+    // (an image has at most 65535 pixels a side and a region lies inside its slot: nothing is lost, and no product below overflows)
+    if (spec->slot_width > 65535u || spec->slot_height > 65535u)
+        return fail(COMPEG_E_INVALID_ARG, ("crop regions spec: the slot " + slot + " is beyond 65535 pixels a side, which no image has").c_str());
+    CropSlotLayout l;
+    if (spec->format == COMPEG_CROP_RGB_PLANAR) {
+        if (spec->pitch != 0u)
+            return fail(COMPEG_E_INVALID_ARG, ("crop regions spec: pitch " + std::to_string(spec->pitch) + " with the planar format, whose rows are tight (pitch 0)").c_str());
+        l.pitch = spec->slot_width;
+        l.slot_bytes = 3ull * spec->slot_width * spec->slot_height;
+    } else {
+        const uint32_t row = 4u * spec->slot_width;
+        if (spec->pitch != 0u && (spec->pitch < row || spec->pitch % 4u != 0u))
+            return fail(COMPEG_E_INVALID_ARG, ("crop regions spec: pitch " + std::to_string(spec->pitch) + " is not a multiple of 4 at or above the slot row's " +
+                                               std::to_string(row) + " bytes").c_str());
+        l.pitch = spec->pitch ? spec->pitch : row;
+        l.slot_bytes = uint64_t(l.pitch) * spec->slot_height;
+    }
+    *out = l;
+    return COMPEG_OK;
+}
+
+// One region against its width x height image and the (checked) spec's slot; which: "region 3: " or "".
+int crop_region_fits(const compeg_crop_regions_spec &spec, uint32_t width, uint32_t height, const compeg_crop_region &r, const std::string &which)
+{
+    const std::string rect = std::to_string(r.width) + "x" + std::to_string(r.height) + " at (" + std::to_string(r.x) + ", " + std::to_string(r.y) + ")";
+    if (r.reserved != 0u)
+        return fail(COMPEG_E_INVALID_ARG, ("crop regions: " + which + "reserved is " + std::to_string(r.reserved) + ", it must be 0").c_str());
+    if (r.width == 0 || r.height == 0)
+        return fail(COMPEG_E_INVALID_ARG, ("crop regions: " + which + "the rectangle " + rect + " is empty").c_str());
+    if (uint64_t(r.x) + r.width > width || uint64_t(r.y) + r.height > height)
+        return fail(COMPEG_E_INVALID_ARG, ("crop regions: " + which + "the rectangle " + rect + " reaches beyond image " + std::to_string(r.image) + "'s " +
+                                           std::to_string(width) + "x" + std::to_string(height)).c_str());
+    if (uint64_t(r.dst_x) + r.width > spec.slot_width || uint64_t(r.dst_y) + r.height > spec.slot_height)
+        return fail(COMPEG_E_INVALID_ARG, ("crop regions: " + which + "the rectangle " + rect + " placed at (" + std::to_string(r.dst_x) + ", " +
+                                           std::to_string(r.dst_y) + ") reaches beyond the slot's " + std::to_string(spec.slot_width) + "x" +
+                                           std::to_string(spec.slot_height)).c_str());
+    return COMPEG_OK;
+}
+
+// What the checks and the records need of an image: its extent, its luma sampling as the kernels take it (1 x 0: a
+// grayscale image) and its restart intervals.
+struct RegionImage {
+    uint32_t width, height, hs, vs, intervals;
+};
+RegionImage region_image(const ImageDesc &d)
+{
+    const bool gray = d.dus_per_mcu == 1;
+    return RegionImage{d.out_w, d.out_h, gray ? 1u : d.hsample[0], gray ? 0u : d.vsample[0], d.total_intervals};
+}
+RegionImage region_image(const ImageData &data)
+{
+    const bool gray = data.components == 1;
+    return RegionImage{data.width, data.height, gray ? 1u : data.metadata.components[0].hsample, gray ? 0u : data.metadata.components[0].vsample,
+                       data.metadata.total_restart_intervals};
+}
+
+// The whole validation, once for both owners: 0 with *call made -- the records grouped by their image's sampling, a
+// stable grouping, each with its own place in the destination -- or the error recorded.  images: the upload's count;
+// image_of(i): image i.  Nothing of the caller's is kept: the records are copies.
+template <class ImageOf>
+int crop_regions_call(const compeg_crop_regions_spec *spec, const compeg_crop_region *regions, size_t count, size_t images, const ImageOf &image_of,
+                      void *device_dst, size_t dst_bytes, CropRegionsCall *call)
+{
+    CropSlotLayout l;
+    int rc = crop_regions_layout(spec, &l);
+    if (rc != COMPEG_OK)
+        return rc;
+    if (!device_dst)
+        return fail(COMPEG_E_INVALID_ARG, "device_dst is NULL");
+    if (count != 0 && !regions)
+        return fail(COMPEG_E_INVALID_ARG, "regions is NULL");
+    if (spec->format == COMPEG_CROP_RGBA && reinterpret_cast<uintptr_t>(device_dst) % 4u != 0u)
+        return fail(COMPEG_E_INVALID_ARG, "crop regions: the rgba destination's address is not a multiple of 4");
+    if (uint64_t(dst_bytes) / l.slot_bytes < count)
+        return fail(COMPEG_E_INVALID_ARG, ("crop regions: dst_bytes is " + std::to_string(dst_bytes) + ", " + std::to_string(count) + " slot(s) of " +
+                                           std::to_string(l.slot_bytes) + " bytes need " + std::to_string(l.slot_bytes * count)).c_str());
+    std::vector<CropRegionPlace> places(count);
+    for (size_t k = 0; k < count; k++) {
+        const compeg_crop_region &r = regions[k];
+        const std::string which = "region " + std::to_string(k) + ": ";
+        if (r.image >= images)
+            return fail(COMPEG_E_INVALID_ARG, ("crop regions: " + which + "image " + std::to_string(r.image) + " is beyond the upload's " +
+                                               std::to_string(images) + " image(s)").c_str());
+        const RegionImage im = image_of(r.image);
+        rc = crop_region_fits(*spec, im.width, im.height, r, which);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (crop_region_group(im.hs, im.vs) == kCropRegionGroups)
+            return fail(COMPEG_E_UNSUPPORTED, ("crop regions: " + which + "image " + std::to_string(r.image) + "'s luma sampling " + std::to_string(im.hs) +
+                                               "x" + std::to_string(im.vs) + " has no cropped kernel").c_str());
+        places[k] = CropRegionPlace{r.image, r.x, r.y, r.width, r.height, r.dst_x, r.dst_y, im.hs, im.vs, im.intervals};
+    }
+    const CropRegionsTarget target{static_cast<uint8_t *>(device_dst), uint64_t(spec->slot_width) * spec->slot_height, l.pitch, spec->format};
+    *call = make_crop_regions_call(target, l.slot_bytes, spec->format == COMPEG_CROP_RGBA ? 4u : 1u, places.data(), count);
+    return COMPEG_OK;
+}
+
+int decoder_cropped_regions(compeg_decoder *dec, const compeg_image *img, const compeg_crop_regions_spec *spec, const compeg_crop_region *regions,
+                            size_t count, void *device_dst, size_t dst_bytes, void *hip_stream, bool blocking)
+{
+    return guarded([&] {
+        if (!dec || !img)
+            return fail(COMPEG_E_INVALID_ARG, "NULL argument");
+        const RegionImage im = region_image(*img->data);
+        CropRegionsCall call;
+        const int rc = crop_regions_call(spec, regions, count, 1, [&](uint32_t) { return im; }, device_dst, dst_bytes, &call);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (count == 0)
+            return ok();
+        const hipStream_t stream = stream_of(*dec, hip_stream);
+        const Status s = dec->decode_cropped_regions(*img->data, call, stream);
+        if (!s.ok())
+            return fail(s);
+        const hipError_t e = blocking ? hipStreamSynchronize(stream) : hipSuccess;
+        return e == hipSuccess ? ok() : fail(hip_status(e, "hipStreamSynchronize"));
+    });
+}
+
+} // namespace
+
+extern "C" {
+
+int compeg_crop_regions_shape(const compeg_crop_regions_spec *spec, uint32_t *pitch, uint64_t *slot_bytes)
+{
+    return guarded([&] {
+        CropSlotLayout l;
+        const int rc = crop_regions_layout(spec, &l);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (pitch)
+            *pitch = l.pitch;
+        if (slot_bytes)
+            *slot_bytes = l.slot_bytes;
+        return ok();
+    });
+}
+
+int compeg_crop_region_check(const compeg_crop_regions_spec *spec, uint32_t image_width, uint32_t image_height, const compeg_crop_region *region)
+{
+    return guarded([&] {
+        CropSlotLayout l;
+        const int rc = crop_regions_layout(spec, &l);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (!region)
+            return fail(COMPEG_E_INVALID_ARG, "region is NULL");
+        if (image_width == 0 || image_height == 0)
+            return fail(COMPEG_E_INVALID_ARG, "crop regions: the image has no pixels");
+        return crop_region_fits(*spec, image_width, image_height, *region, "");
+    });
+}
+
+int compeg_batch_decode_cropped_regions(compeg_batch *batch, const compeg_crop_regions_spec *spec, const compeg_crop_region *regions, size_t count,
+                                        void *device_dst, size_t dst_bytes, void *hip_stream)
+{
+    return guarded([&] {
+        if (!batch)
+            return fail(COMPEG_E_INVALID_ARG, null_text(batch));
+        const Status up = batch->finish_upload(); // (the descriptors looked at below are the finished upload's)
+        if (!up.ok())
+            return fail(up);
+        if (batch->count == 0 && count != 0)
+            return fail(COMPEG_E_INVALID_ARG, "crop regions: nothing uploaded yet");
+        CropRegionsCall call;
+        const int rc = crop_regions_call(spec, regions, count, batch->count, [&](uint32_t i) { return region_image(batch->descs[i]); }, device_dst,
+                                         dst_bytes, &call);
+        if (rc != COMPEG_OK)
+            return rc;
+        if (count == 0)
+            return ok();
+        const Status s = batch->decode_cropped_regions(call, stream_of(*batch, hip_stream));
+        return s.ok() ? ok() : fail(s);
+    });
+}
+
+int compeg_decoder_decode_cropped_regions(compeg_decoder *dec, const compeg_image *img, const compeg_crop_regions_spec *spec,
+                                          const compeg_crop_region *regions, size_t count, void *device_dst, size_t dst_bytes, void *hip_stream)
+{
+    return decoder_cropped_regions(dec, img, spec, regions, count, device_dst, dst_bytes, hip_stream, false);
+}
+
+int compeg_decoder_decode_cropped_regions_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_crop_regions_spec *spec,
+                                                   const compeg_crop_region *regions, size_t count, void *device_dst, size_t dst_bytes)
+{
+    return decoder_cropped_regions(dec, img, spec, regions, count, device_dst, dst_bytes, nullptr, true);
+}
+
+} // extern "C"

@@ -61,21 +61,36 @@ CG_DEV uint32_t crop_lane_own(uint32_t v)
 #endif
 }
 
+// What the rectangle's pixels are laid into: bytes from row to row (planar: the rows' width) and, planar, the bytes from
+// plane to plane.  A destination that holds the rectangle alone has the rectangle's own (CropOwnSlot: the one-rectangle
+// decode); a region of a list lies in a slot that is larger than it (crop_regions_body.h).  The wave function is handed
+// the maker, not the values, and asks it where it fills CropEdges: the one-rectangle kernels then compute the plane where
+// they always have, behind the entropy decode's set-up, and hold no scalar register for it before.
+struct CropSlot {
+    uint32_t pitch;
+    uint64_t plane;
+};
+struct CropOwnSlot {};
+CG_DEV CropSlot crop_slot(const CropOwnSlot &, const CropTarget &g)
+{
+    return CropSlot{g.pitch, uint64_t(g.width) * g.height};
+}
+
 // The rectangle's edges in pixels of the image, x0 <= X < x1 and y0 <= Y < y1, the destination's pitch and the bytes of
 // one of its planes: the lane's copy (crop_lane_own).
 struct CropEdges {
     uint32_t x0, x1, y0, y1, pitch;
-    uint32_t plane_lo, plane_hi; // (planar: the bytes of one plane, width x height)
-    uint8_t *img;                // the image's first byte in the destination
+    uint32_t plane_lo, plane_hi; // (planar: the bytes from plane to plane -- CropSlot's)
+    uint8_t *img;                // the rectangle's first byte in the destination
     uint32_t width_mcus;         // (ImageDesc's)
 };
 
-// (img: where this image of the launch begins)
-CG_DEV CropEdges crop_edges(const ImageDesc &d, const CropTarget &g, uint8_t *img)
+// (img: where this image's rectangle begins; slot: what it is laid into)
+CG_DEV CropEdges crop_edges(const ImageDesc &d, const CropTarget &g, const CropSlot &slot, uint8_t *img)
 {
-    const uint64_t plane = uint64_t(g.width) * g.height, at = reinterpret_cast<uintptr_t>(img);
+    const uint64_t plane = slot.plane, at = reinterpret_cast<uintptr_t>(img);
     const uint64_t own = uint64_t(crop_lane_own(uint32_t(at >> 32))) << 32 | crop_lane_own(uint32_t(at));
-    return CropEdges{crop_lane_own(g.x), crop_lane_own(g.x + g.width), crop_lane_own(g.y), crop_lane_own(g.y + g.height), crop_lane_own(g.pitch),
+    return CropEdges{crop_lane_own(g.x), crop_lane_own(g.x + g.width), crop_lane_own(g.y), crop_lane_own(g.y + g.height), crop_lane_own(slot.pitch),
                      crop_lane_own(uint32_t(plane)), crop_lane_own(uint32_t(plane >> 32)), reinterpret_cast<uint8_t *>(uintptr_t(own)), crop_lane_own(d.width_mcus)};
 }
 
@@ -252,8 +267,10 @@ CG_DEV void crop_next_mcu(CropMcu<HS, VS> &t, const CropEdges &c)
 // image's last, does nothing; a touched one stops behind its last MCU in the box.  The lanes of a wave thus leave the
 // loop at different counts: nothing in it goes from lane to lane (no quad exchange, lane-local stores), and what stays
 // wave-uniform is the data unit's place in its MCU, the same in every lane that is still walking.
-template <int HS, int VS>
-CG_DEV void decode_wave_cropped(const ImageDesc &d, const HuffShared &s, const CropTarget &g, uint8_t *img, uint32_t interval, uint32_t lane)
+// g: the rectangle, its box of MCUs and the format (its pitch is not read here: `into`'s is).
+template <int HS, int VS, class Into>
+CG_DEV void decode_wave_cropped(const ImageDesc &d, const HuffShared &s, const CropTarget &g, const Into &into, uint8_t *img, uint32_t interval,
+                                uint32_t lane)
 {
     constexpr uint32_t kDus = uint32_t(CropMcu<HS, VS>::kDus), kLuma = uint32_t(CropMcu<HS, VS>::kLuma);
     const uint32_t reach = interval < d.total_intervals ? crop_intervals_reach(d, g, interval, 1u) : 0u;
@@ -264,7 +281,7 @@ CG_DEV void decode_wave_cropped(const ImageDesc &d, const HuffShared &s, const C
     zero_slot(slot);
     EntropyState e;
     entropy_init(e, d, s, interval);
-    const CropEdges c = crop_edges(d, g, img);
+    const CropEdges c = crop_edges(d, g, crop_slot(into, g), img);
     CropMcu<HS, VS> t;
     crop_init<HS, VS>(t, d, c, interval);
     const uint32_t du_total = reach * kDus;
@@ -283,6 +300,13 @@ CG_DEV void decode_wave_cropped(const ImageDesc &d, const HuffShared &s, const C
             k++;
         }
     }
+}
+
+// ... into a destination that holds the rectangle alone.
+template <int HS, int VS>
+CG_DEV void decode_wave_cropped(const ImageDesc &d, const HuffShared &s, const CropTarget &g, uint8_t *img, uint32_t interval, uint32_t lane)
+{
+    decode_wave_cropped<HS, VS>(d, s, g, CropOwnSlot{}, img, interval, lane);
 }
 
 } // namespace compeg

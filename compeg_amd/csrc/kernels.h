@@ -6,6 +6,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "compeg_hip.h"
+#include "crop_regions_types.h"
 #include "crop_types.h"
 #include "device_types.h"
 #include "levels_types.h"
@@ -229,6 +230,15 @@ hipError_t launch_reduced(const ImageDesc *descs, uint32_t images, uint32_t max_
 uint32_t crop_wave_cap(uint32_t hs, uint32_t vs);
 hipError_t launch_cropped(const ImageDesc *descs, uint32_t images, uint32_t max_intervals, const HuffLdsPlan &plan, uint32_t hs, uint32_t vs,
                           const CropTarget &target, hipStream_t stream);
+
+// Cropped decode of a region list (crop_regions_kernels.hip, crop_regions_body.h): `regions` records from `records` on
+// (device memory), all of images of one luma sampling -- group: crop_region_group's -- each a rectangle of the image
+// descs[record.image] into the place its record's offset names; the cropped decode's prologue and lane body.
+// max_intervals: the largest interval count among the images the records name; at most 65535 regions a launch; plan:
+// plan_huffman's with wave_cap = crop_regions_wave_cap.  records and target: validated by the caller.
+uint32_t crop_regions_wave_cap(uint32_t hs, uint32_t vs);
+hipError_t launch_cropped_regions(const ImageDesc *descs, const CropRegionRecord *records, uint32_t regions, uint32_t max_intervals,
+                                  const HuffLdsPlan &plan, uint32_t group, const CropRegionsTarget &target, hipStream_t stream);
 
 // Scaled decode (scaled_kernels.hip, scaled_body.h): the images at 1/2 or 1/4 scale, target.n x target.n pixels per luma
 // data unit from an n-point inverse DCT of each data unit's lowest frequencies, into the caller's memory as `target` lays

@@ -1444,6 +1444,8 @@ Status compeg_batch::upload_host(size_t n, int threads, const void *items_, cons
     max_intervals = max_dus = max_l2 = 0;
     algorithmic_bytes = pixels = 0;
     max_span = 0;
+    image_span.assign(n, 0);
+    image_l2.assign(n, 0);
     for (size_t i = 0; i < n; i++) {
         if (!results[i].ok() && results[i].code != COMPEG_E_COUNT_MISMATCH) {
             (void)hipStreamSynchronize(st);
@@ -1455,6 +1457,8 @@ Status compeg_batch::upload_host(size_t n, int threads, const void *items_, cons
         max_l2 = std::max<uint32_t>(max_l2, staged_lut_entries(img));
         pixels += uint64_t(img.width) * img.height;
         max_span = std::max(max_span, spans[i]);
+        image_span[i] = spans[i];
+        image_l2[i] = staged_lut_entries(img);
         algorithmic_bytes += alg[i];
     }
     note_batch_properties(got.data(), n);
@@ -1936,6 +1940,8 @@ Status compeg_batch::upload_device_scan(size_t n, int threads, const FeedSource 
         // (while the last quarter arrives: everything about the batch that needs the headers only)
         max_tiles = 0;
         max_intervals = max_dus = max_l2 = max_span = 0;
+        image_span.assign(n, 0);
+        image_l2.assign(n, 0);
         algorithmic_bytes = pixels = 0;
         size_t out_total = 0;
         bool all_covered = true;
@@ -2025,6 +2031,8 @@ Status compeg_batch::upload_device_scan(size_t n, int threads, const FeedSource 
             d.out_pitch = output_pitch(img.width);
             d.out_alloc_h = output_rows(img.height);
             max_span = std::max(max_span, span);
+            image_span[i] = span;
+            image_l2[i] = staged_lut_entries(img);
             if (i == 0) {
                 coop_r = img.metadata.restart_interval;
                 coop_spans = CoopSpans{};
@@ -2353,6 +2361,97 @@ Status compeg_batch::decode_into(const CallerDecode &into, uint32_t hs, uint32_t
     last_kernel = into.kernel_id;
     decode_recorded = true; // (something of the batch's is on last_stream: what order_pack_behind_decode asks)
     return note_pack(stream);
+}
+
+// Cropped decode of a region list (compeg_hip.h, "Cropped decode of a region list"; the call validated and its records
+// grouped by the C layer: crop_regions_types.h).  One road for both owners: behind the owner's previous work, the records
+// go to the device in stream order through the owner's RecordStage, then one launch per sampling present among the
+// regions' images, each split at `chunk` regions (0: none) and at the grid's y limit; plan_for(regions): the owner's
+// plan for a launch of that many rows.
+template <class PlanFor>
+static hipError_t launch_crop_region_groups(const CropRegionsCall &call, const void *device_records, const ImageDesc *dev_descs, uint32_t chunk,
+                                            const PlanFor &plan_for, hipStream_t stream)
+{
+    constexpr uint32_t kGridRows = 65535;
+    const CropRegionRecord *records = static_cast<const CropRegionRecord *>(device_records);
+    for (uint32_t g = 0; g < kCropRegionGroups; g++) {
+        const uint32_t n = call.count[g], step = std::min(chunk ? chunk : kGridRows, kGridRows);
+        for (uint32_t at = 0; at < n; at += step) {
+            const uint32_t m = std::min(step, n - at);
+            const hipError_t e = launch_cropped_regions(dev_descs, records + at, m, call.intervals[g], plan_for(m, g), g, call.target, stream);
+            if (e != hipSuccess)
+                return e;
+        }
+        records += n;
+    }
+    return hipSuccess;
+}
+
+template <class Owner>
+static Status send_crop_region_records(Owner &owner, const CropRegionsCall &call, hipStream_t stream, const void **device_records)
+{
+    CG_TRY(owner.order_pack_behind_decode(stream));
+    return owner.crop_records.upload(call.records.data(), call.records.size() * sizeof(CropRegionRecord), stream, device_records);
+}
+
+// The batch: the images of the last upload, planned with the batch's own maxima as decode_into plans; ordered like a
+// pack, no timing events, `out` untouched.
+Status compeg_batch::decode_cropped_regions(const CropRegionsCall &call, hipStream_t stream)
+{
+    CG_TRY(finish_upload());
+    if (count == 0 || call.records.empty())
+        return Status{};
+    CG_HIP(hipSetDevice(gpu->device));
+    const void *records = nullptr;
+    CG_TRY(send_crop_region_records(*this, call, stream, &records));
+    if (preprocess_mode == 2 && host_fallbacks == 0)
+        CG_HIP(launch_scan(static_cast<const ScanDesc *>(scan_descs.ptr), uint32_t(count), max_tiles, stream));
+    // A group's launches are planned with the maxima of the images the group names, not the batch's: a launch of 4:2:2
+    // frames planned with the window of 4:2:0 frames twice their intervals' length holds a third of the waves a CU could
+    // (5.3 x the time on 128 4K 4:2:2 frames beside 128 1080p 4:2:0 ones).  The batch's when an upload
+    // road has not noted its images' values.
+    uint32_t group_l2[kCropRegionGroups], group_span[kCropRegionGroups];
+    const bool noted = image_span.size() == count && image_l2.size() == count;
+    const CropRegionRecord *r = call.records.data();
+    for (uint32_t g = 0; g < kCropRegionGroups; g++) {
+        group_l2[g] = noted ? 0u : max_l2;
+        group_span[g] = noted ? 0u : max_span;
+        for (uint32_t k = 0; k < call.count[g]; k++, r++) {
+            if (!noted)
+                continue;
+            group_l2[g] = std::max(group_l2[g], image_l2[r->image]);
+            group_span[g] = std::max(group_span[g], image_span[r->image]);
+        }
+    }
+    CG_HIP(launch_crop_region_groups(call, records, static_cast<const ImageDesc *>(dev_descs.ptr), chunk,
+                                     [&](uint32_t m, uint32_t g) {
+                                         return plan_huffman(call.intervals[g], m, group_l2[g], group_span[g], true,
+                                                             crop_regions_wave_cap(kCropRegionGroupHs[g], kCropRegionGroupVs[g]));
+                                     },
+                                     stream));
+    last_kernel = COMPEG_KERNEL_CROPPED;
+    decode_recorded = true; // (something of the batch's is on last_stream: what order_pack_behind_decode asks)
+    return note_pack(stream);
+}
+
+// The decoder: enqueue's road for a decode into the caller's memory (upload, preprocessing, plan, the events behind it)
+// with the groups' launches -- one group: one image -- in the decode kernel's place.
+Status compeg_decoder::decode_cropped_regions(const ImageData &img, const CropRegionsCall &call, hipStream_t stream)
+{
+    CG_HIP(hipSetDevice(gpu->device));
+    struct Road {
+        const CropRegionsCall *call;
+        const void *records;
+    } road{&call, nullptr};
+    CG_TRY(send_crop_region_records(*this, call, stream, &road.records));
+    CallerDecode into{&road,
+                      [](const void *target, uint32_t, const ImageDesc *descs, uint32_t, uint32_t, const HuffLdsPlan &plan, uint32_t, uint32_t,
+                         hipStream_t st) {
+                          const Road &r = *static_cast<const Road *>(target);
+                          return launch_crop_region_groups(*r.call, r.records, descs, 0, [&](uint32_t, uint32_t) { return plan; }, st);
+                      },
+                      true, crop_regions_wave_cap, COMPEG_KERNEL_CROPPED};
+    return enqueue(img, stream, nullptr, false, &into);
 }
 
 // Tensor output.  Every pack reads `out` on a stream of the caller's choice: behind the last decode (the scheme of

@@ -153,6 +153,10 @@ struct compeg_decoder {
     compeg::Status enqueue(const compeg::ImageData &img, hipStream_t stream, bool *changed, bool may_defer = false,
                            const compeg::CallerDecode *into = nullptr);
     compeg::Status finish_deferred(const compeg::ImageData &img, hipStream_t stream);
+    // Cropped decode of a region list (compeg_hip.h; crop_regions_types.h: the call, validated by the caller, every
+    // record's image 0): enqueue's road for a decode into the caller's memory, the records through crop_records
+    compeg::RecordStage crop_records;
+    compeg::Status decode_cropped_regions(const compeg::ImageData &img, const compeg::CropRegionsCall &call, hipStream_t stream);
     // Tensor output (compeg_hip.h): the last image's corner of `out`, packed on `stream` behind the last decode; the next
     // decode waits for it.  spec and dst: checked by the caller.
     compeg::Status pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream);
@@ -282,6 +286,15 @@ struct compeg_batch {
     // (hs x vs; 1 x 0: grayscale), checked by the caller like the target.  Chunks and preprocessing mode 2 as in decode();
     // ordered like a pack; no timing events; `out` untouched.
     compeg::Status decode_into(const compeg::CallerDecode &into, uint32_t hs, uint32_t vs, hipStream_t stream);
+    // Cropped decode of a region list (compeg_hip.h; crop_regions_types.h: the call, validated by the caller): images of
+    // any mix of sizes and samplings, a launch per sampling present, `chunk` bounding the regions of a launch; mode 2's
+    // scan launch in front, once; ordered like a pack; no timing events; `out` untouched.  The records travel through
+    // crop_records.
+    compeg::RecordStage crop_records;
+    compeg::Status decode_cropped_regions(const compeg::CropRegionsCall &call, hipStream_t stream);
+    // ... planned per sampling group with the maxima of the images the group names: every image's largest wave span and
+    // its staged LUT entries, noted by the upload roads beside max_span and max_l2
+    std::vector<uint32_t> image_span, image_l2;
     // Tensor output (compeg_hip.h): every image's output (all of one size: checked by the caller, like spec and dst)
     compeg::Status pack_tensor(const compeg_tensor_spec &spec, void *dst, hipStream_t stream);
     // ... and every pack's ordering, in the batch's own scheme (it records decode_done only when a stream changes): `stream`

@@ -933,8 +933,9 @@ int compeg_crop_shape(const compeg_crop_spec *spec, uint32_t image_width, uint32
  * Known limits: the scan preprocessing still reads the whole entropy-coded segment, since every interval's start comes
  * from it -- the saving is in the decode kernel; a touched interval is walked from its start up to its last MCU in the
  * rectangle, so a file without DRI or with long intervals saves little; a lane per restart interval on every launch
- * (no cooperative, walk or streamed-window form); one rectangle a call; no mixed sizes or samplings; no cropped planes
- * or reduced output; the tensor packs do not read a caller's image. */
+ * (no cooperative, walk or streamed-window form); no cropped planes or reduced output; the tensor packs do not read a
+ * caller's image.  (A rectangle per image, several per image, images of mixed sizes and samplings: "Cropped decode of a
+ * region list" below.) */
 int compeg_batch_decode_cropped(compeg_batch *batch, const compeg_crop_spec *spec, void *device_dst, size_t dst_bytes,
                                 void *hip_stream);
 /* One image: uploads and preprocesses as compeg_decoder_enqueue does (host or device preprocessing), records the
@@ -947,6 +948,83 @@ int compeg_decoder_decode_cropped(compeg_decoder *dec, const compeg_image *img, 
                                   size_t dst_bytes, void *hip_stream);
 int compeg_decoder_decode_cropped_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_crop_spec *spec,
                                            void *device_dst, size_t dst_bytes);
+
+/* ---- Cropped decode of a region list (extension) -------------------------------
+ * The cropped decode with a rectangle per region: each region names its image and its rectangle and gets a slot of its
+ * own in the destination.  A loader's random crop per image, a detector's M boxes out of whichever frames hold them, a
+ * dataset of photographs of many sizes with 4:2:0, 4:4:4 and grayscale files side by side.  New entry points beside the
+ * old ones: without these calls nothing behaves differently.
+ *
+ * Destination.  Region k owns slot k, at device_dst + k * slot_bytes; every slot is slot_width x slot_height pixels.
+ *   RGBA        slot_height rows of 4 * slot_width bytes at pitch (0 = tight); slot_bytes = pitch * slot_height.
+ *               device_dst and pitch must be multiples of 4 and pitch >= 4 * slot_width.
+ *   RGB_PLANAR  a tight [3, slot_height, slot_width] u8 block at any address; slot_bytes = 3 * slot_width *
+ *               slot_height.  pitch must be 0.
+ * So [count, slot_height, slot_width, 4] or [count, 3, slot_height, slot_width] is a tensor as it stands.
+ *
+ * Pixels.  Pixel (dst_x + i, dst_y + j) of slot k, 0 <= i < width, 0 <= j < height, is pixel (x + i, y + j) of the RGBA
+ * decode of image regions[k].image, byte for byte, A = 255.  Everything "Cropped decode" says about the entropy quirks,
+ * the DC predictor's wrap, intervals beyond the scan's restart markers and grayscale files applies unchanged.
+ *
+ * Rectangles.  Each is non-empty and lies inside its image; dst_x + width <= slot_width and dst_y + height <=
+ * slot_height.  Any number of regions may name the same image, in any order; an image may be named by none.  x, y,
+ * dst_x and dst_y need not be aligned to anything.
+ *
+ * NOT WRITTEN: everything in a slot outside its region's rectangle -- the rest of the slot (a pad colour the caller put
+ * there stays), the rest of a row inside its pitch -- and anything in front of or behind the destination; and the
+ * pixels of MCUs behind the image's last complete restart interval.
+ *
+ * The images may differ in size, sampling (4:2:2, 4:4:4, 4:4:0, 4:2:0, grayscale), entropy mode and tables. */
+typedef struct compeg_crop_region {
+    uint32_t image;               /* index into the batch's last upload (decoder: 0) */
+    uint32_t x, y, width, height; /* the rectangle, in pixels of that image */
+    uint32_t dst_x, dst_y;        /* where its top-left pixel lies in its slot */
+    uint32_t reserved;            /* 0 */
+} compeg_crop_region;             /* 32 bytes */
+typedef struct compeg_crop_regions_spec {
+    uint32_t slot_width, slot_height; /* every region's slot, in pixels (1 .. 65535) */
+    uint32_t format;                  /* COMPEG_CROP_RGBA / COMPEG_CROP_RGB_PLANAR */
+    uint32_t pitch;                   /* RGBA: bytes from row to row of a slot, 0 = tight; RGB_PLANAR: 0 */
+    uint32_t reserved[4];             /* 0 */
+} compeg_crop_regions_spec;           /* 32 bytes */
+/* No device needed: checks the spec and gives the pitch that will be used (RGB_PLANAR: slot_width) and one slot's
+ * bytes.  Either output may be NULL.  COMPEG_E_INVALID_ARG, with a message that states the values, for: a NULL spec, a
+ * format out of range, reserved not 0, a slot extent of 0 or above 65535 (no image has more pixels a side), RGB_PLANAR
+ * with a pitch, an RGBA pitch below 4 * slot_width or not a multiple of 4.  Nothing is written on failure. */
+int compeg_crop_regions_shape(const compeg_crop_regions_spec *spec, uint32_t *pitch, uint64_t *slot_bytes);
+/* No device needed: the spec as above, then one region against an image_width x image_height image and the slot.
+ * COMPEG_E_INVALID_ARG with a message that states the values for: a NULL region, an image without pixels, reserved not
+ * 0, an empty rectangle, a rectangle that reaches beyond the image, a rectangle that placed at (dst_x, dst_y) reaches
+ * beyond the slot.  region->image is not looked at. */
+int compeg_crop_region_check(const compeg_crop_regions_spec *spec, uint32_t image_width, uint32_t image_height,
+                             const compeg_crop_region *region);
+/* `count` regions of the images of the batch's last upload, region k into slot k.  Refused with COMPEG_E_INVALID_ARG
+ * and a message that states the values -- nothing is launched or written, whichever region is the bad one, and a
+ * refusal that concerns one region names its index: what the two functions above refuse; a NULL batch, device_dst, or
+ * regions with count > 0; an RGBA device_dst that is not a multiple of 4; a region whose image is at or beyond the
+ * upload's count; dst_bytes below count * slot_bytes (the message names both numbers); nothing uploaded yet.
+ * count == 0 succeeds and launches nothing.  The regions are copied during the call: the caller may free them on return.
+ * Records on hip_stream (NULL = the gpu's stream) and returns without waiting; compeg_batch_wait covers it.  One launch
+ * per sampling present among the images the regions name, at most five; compeg_batch_set_chunk(n) bounds the REGIONS
+ * per launch for this call; the three preprocessing modes work as for compeg_batch_decode.  Ordering is the tensor
+ * packs', both ways, as for compeg_batch_decode_cropped; no timing events are recorded; the RGBA output and what the
+ * packs see as the last decode are left alone.  compeg_batch_last_kernel then says COMPEG_KERNEL_CROPPED.
+ * Known limits: one region a slot (no mosaics of several regions in one slot); no scale per region (crop x
+ * decode_scaled); no cropped planes or levels; the planes, reduced, scaled and levels decodes still want batches of one
+ * size and sampling; regions of the same image share nothing -- each walks its touched intervals itself; a lane per
+ * restart interval on every launch (no cooperative, walk or streamed form), so a file without DRI or with long
+ * intervals saves little, as for the one-rectangle decode; the tensor packs do not read a caller's image. */
+int compeg_batch_decode_cropped_regions(compeg_batch *batch, const compeg_crop_regions_spec *spec, const compeg_crop_region *regions,
+                                        size_t count, void *device_dst, size_t dst_bytes, void *hip_stream);
+/* One image, M boxes of it: every region's image must be 0.  Uploads and preprocesses as compeg_decoder_decode_cropped
+ * does and records the decode on hip_stream; the _blocking form records on the gpu's stream and waits.  The texture, its
+ * extent and what the packs read stay those of the last RGBA decode; ordering as for compeg_decoder_decode_cropped.
+ * compeg_decoder_last_kernel then says COMPEG_KERNEL_CROPPED. */
+int compeg_decoder_decode_cropped_regions(compeg_decoder *dec, const compeg_image *img, const compeg_crop_regions_spec *spec,
+                                          const compeg_crop_region *regions, size_t count, void *device_dst, size_t dst_bytes,
+                                          void *hip_stream);
+int compeg_decoder_decode_cropped_regions_blocking(compeg_decoder *dec, const compeg_image *img, const compeg_crop_regions_spec *spec,
+                                                   const compeg_crop_region *regions, size_t count, void *device_dst, size_t dst_bytes);
 
 /* ---- Scaled decode (extension) ------------------------------------------------
  * A fifth kind of decode: the image at 1/2, 1/4 or 1/8 scale, written into caller-owned device memory.  What libjpeg

@@ -187,6 +187,32 @@ pub struct compeg_crop_spec {
     pub reserved: [u32; 2],
 }
 
+/// One region of a cropped decode of a region list (compeg_hip.h, "Cropped decode of a region list"): the rectangle in
+/// pixels of image `image` and where its top-left pixel lies in its slot; `reserved` is 0.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct compeg_crop_region {
+    pub image: u32,
+    pub x: u32,
+    pub y: u32,
+    pub width: u32,
+    pub height: u32,
+    pub dst_x: u32,
+    pub dst_y: u32,
+    pub reserved: u32,
+}
+
+/// Every region's slot in pixels, the format and the RGBA row pitch in bytes (0 = tight); `reserved` is 0.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct compeg_crop_regions_spec {
+    pub slot_width: u32,
+    pub slot_height: u32,
+    pub format: u32,
+    pub pitch: u32,
+    pub reserved: [u32; 4],
+}
+
 pub const COMPEG_OK: c_int = 0;
 pub const COMPEG_E_INVALID_ARG: c_int = -1;
 pub const COMPEG_E_UNSUPPORTED: c_int = -2;
@@ -452,6 +478,18 @@ extern "C" {
                                          device_dst: *mut c_void, dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
     pub fn compeg_decoder_decode_cropped_blocking(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_crop_spec,
                                                   device_dst: *mut c_void, dst_bytes: usize) -> c_int;
+    pub fn compeg_crop_regions_shape(spec: *const compeg_crop_regions_spec, pitch: *mut u32, slot_bytes: *mut u64) -> c_int;
+    pub fn compeg_crop_region_check(spec: *const compeg_crop_regions_spec, image_width: u32, image_height: u32,
+                                    region: *const compeg_crop_region) -> c_int;
+    pub fn compeg_batch_decode_cropped_regions(batch: *mut compeg_batch, spec: *const compeg_crop_regions_spec,
+                                               regions: *const compeg_crop_region, count: usize, device_dst: *mut c_void,
+                                               dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_decoder_decode_cropped_regions(dec: *mut compeg_decoder, img: *const compeg_image, spec: *const compeg_crop_regions_spec,
+                                                 regions: *const compeg_crop_region, count: usize, device_dst: *mut c_void,
+                                                 dst_bytes: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn compeg_decoder_decode_cropped_regions_blocking(dec: *mut compeg_decoder, img: *const compeg_image,
+                                                          spec: *const compeg_crop_regions_spec, regions: *const compeg_crop_region,
+                                                          count: usize, device_dst: *mut c_void, dst_bytes: usize) -> c_int;
     pub fn compeg_scaled_shape(spec: *const compeg_scaled_spec, width: u32, height: u32, out_width: *mut u32, out_height: *mut u32,
                                pitch: *mut u32, total_bytes: *mut u64) -> c_int;
     pub fn compeg_batch_decode_scaled(batch: *mut compeg_batch, spec: *const compeg_scaled_spec, device_dst: *mut c_void,
