@@ -38,6 +38,12 @@ constexpr uint32_t fast_entry(uint32_t ref, uint32_t zrl_advance)
 constexpr uint32_t kDcFastBits = 9;
 constexpr uint32_t kDcFastEntries = 1u << kDcFastBits;
 
+// LUT entries a lane-per-interval kernel stages in LDS behind L1 at the most (plan_huffman, plan_stream, plan_walk):
+// the L2 LUT, then the two direct AC tables, cut here.  What lies beyond is looked up in global memory
+// (kernels_body.h: lut_lookup<false>), and the fast entropy mode needs both direct tables inside it
+// (fast_tables_usable).  The walk reads its direct tables from LDS alone: runtime.cpp, walk_luts_fit.
+constexpr uint32_t kLutLdsShare = 12288u;
+
 // The cooperative kernel's geometry (coop_body.h), a function of the restart interval alone -- host planning and
 // the kernels compute it the same way.  A walk (a team of `waves` waves; or a lone wave) takes as many whole
 // restart intervals as have 64 x waves data units together -- one interval if it alone is longer -- and decodes

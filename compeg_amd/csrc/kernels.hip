@@ -794,7 +794,7 @@ HuffLdsPlan plan_huffman(uint32_t max_intervals, uint32_t images, uint32_t max_l
 {
     HuffLdsPlan p{};
     // everything behind L1: the L2 LUT and the two direct AC tables (at most 24 KB of LDS)
-    p.l2_entries_in_lds = max_l2 < 12288u ? (max_l2 + 1u) & ~1u : 12288u;
+    p.l2_entries_in_lds = max_l2 < kLutLdsShare ? (max_l2 + 1u) & ~1u : kLutLdsShare;
     const uint32_t tables = (((kL1Entries + p.l2_entries_in_lds) * 2u) + 15u) & ~15u;
     const uint32_t slots = kWave * slot_bytes;
 
@@ -974,7 +974,7 @@ StreamPlan plan_stream(uint32_t max_intervals, uint32_t images, uint32_t max_l2,
     group_waves = group_waves ? std::min(group_waves, cu_waves) : cu_waves;
     const uint32_t groups_per_cu = cu_waves / group_waves;
     StreamPlan p;
-    p.l2_entries_in_lds = max_l2 < 12288u ? (max_l2 + 1u) & ~1u : 12288u;
+    p.l2_entries_in_lds = max_l2 < kLutLdsShare ? (max_l2 + 1u) & ~1u : kLutLdsShare;
     const uint32_t tables = (((kL1Entries + p.l2_entries_in_lds) * 2u) + 15u) & ~15u;
     const DeviceLimits lim = device_limits();
     // How often the rows are staged anew -- behind every MCU, behind its luma and its chroma data units, behind every
@@ -1084,7 +1084,7 @@ WalkPlan plan_walk(uint32_t max_intervals, uint32_t images, uint32_t max_l2, uin
 {
     WalkPlan p;
     const DeviceLimits lim = device_limits();
-    p.l2_entries_in_lds = (std::min(max_l2, 12288u) + 2u * kDcFastEntries + 1u) & ~1u;
+    p.l2_entries_in_lds = (std::min(max_l2, kLutLdsShare) + 2u * kDcFastEntries + 1u) & ~1u;
     p.walk_tables = walk_tables;
     const uint32_t tables = (((((kL1Entries + p.l2_entries_in_lds) * 2u) + 15u) & ~15u) + 31u & ~31u) + (walk_tables ? kWalkWords * 4u : 0u) + 96u;
     const uint32_t waves_per_image = (max_intervals + kWave - 1) / kWave;

@@ -447,6 +447,15 @@ uint32_t staged_lut_entries(const ImageData &img)
     return uint32_t(align_up(img.l2.size() * 2, 4) / 2 + img.ac_fast.size());
 }
 
+// May the walk + lane-per-MCU route take tables of this many staged entries?  Its walk reads the direct AC and DC tables
+// from LDS wherever the L2 LUT ends (coop_body.h: coop_tables, walk_body.h: walk_tabs), and plan_walk stages kLutLdsShare
+// entries at the most, and the direct DC tables: with an L2 LUT of more than 8192 entries the walk would read whatever
+// lies behind them.  Such images go to the other kernels, which look up beyond their staged entries in global memory.
+bool walk_luts_fit(uint32_t staged_entries)
+{
+    return staged_entries <= kLutLdsShare;
+}
+
 } // namespace
 
 } // namespace compeg
@@ -939,7 +948,7 @@ Status compeg_decoder::enqueue(const ImageData &img, hipStream_t stream, bool *c
         // the scan kernels -- a blocking decode with device preprocessing: the second descriptor's word count is theirs to
         // fill in, and they know of one descriptor.)
         const uint64_t mcu_words_avg = (img.scan_len / 4u + std::max<uint64_t>(route_mcus, 1u) - 1u) / std::max<uint64_t>(route_mcus, 1u);
-        const bool route = route_possible && !blob_uploaded && hd.mcu_ok && hd.walk && !lab_env("COMPEG_NO_DECODER_ROUTE") &&
+        const bool route = route_possible && !blob_uploaded && hd.mcu_ok && hd.walk && walk_luts_fit(staged_lut_entries(img)) && !lab_env("COMPEG_NO_DECODER_ROUTE") &&
                            !(coop.usable && coop_preferred(coop, md.total_restart_intervals, 1, md.restart_interval)) &&
                            (md.total_restart_intervals + kWave - 1) / kWave <= 1024u && mcu_words_avg <= 24u &&
                            14.5 * md.restart_interval - 40.0 > double(route_mcus) / 5300.0;
@@ -2109,6 +2118,8 @@ bool use_mcu_route(const compeg_batch &b, uint32_t step, uint32_t smallest)
         const char *e = lab_env("COMPEG_WALK"); // experiment knob: 0 / 1
         return e ? atoi(e) : -1;
     }();
+    if (!walk_luts_fit(b.max_l2))
+        return false; // (the walk's direct tables would not be staged: not a matter of speed)
     if (forced >= 0)
         return forced != 0;
     if (b.one_mcu_intervals || b.min_restart_interval < 2u)

@@ -145,8 +145,129 @@ def table(kind, symbols):
 
 
 def table_set(kind, dc_symbols, ac_symbols):
+    if kind in WIDE_KINDS:
+        return wide_table_set(kind, dc_symbols, ac_symbols)
     dc, act = table(kind, dc_symbols), table(kind, ac_symbols)
     return {0: dc, 1: act, 2: dict(dc), 3: dict(act)}
+
+
+# ---- tables that outgrow their share of LDS ------------------------------------------------------------------------------
+
+# The host (compeg_amd/csrc/front.cpp: HuffmanLut::build) gives every 8-bit prefix that begins a code of more than 8 bits
+# one L2 block of 256 entries and concatenates the blocks of Th0 DC, Th0 AC, Th1 DC, Th1 AC; the kernels stage them in LDS
+# behind L1, and behind them the two direct AC tables of kFastEntries entries each (front.h).  The planners stage at most
+# LDS_SHARE entries (kernels.hip: plan_huffman, plan_stream, plan_walk: `12288u`).  Hence the three regimes of a file:
+L2_BLOCK = 256
+FAST_ENTRIES = 2048                          # front.h: kFastEntries = 1 << kFastBits
+LDS_SHARE = 12288                            # kernels.hip: plan_huffman's l2_entries_in_lds cap
+ALL_STAGED = LDS_SHARE - 2 * FAST_ENTRIES    # 8192: L2 and both direct tables fit -- the fast entropy mode (fast_tables_usable)
+INDEX_SPACE = 1 << 15                        # the delegate index has 15 bits: 128 blocks in all (front.cpp: ImageData::parse)
+
+
+def l2_blocks(lengths):
+    """The L2 blocks HuffmanLut::build makes of {symbol: length}: the distinct 8-bit prefixes of the longer codes."""
+    return len({code >> (n - 8) for (code, n) in canonical(lengths)[2].values() if n > 8})
+
+
+def regime_of(entries):
+    """A: everything staged, the fast mode on.  B: all of L2 staged, the direct tables in part, the fast mode off.  C: L2
+    lookups at and beyond LDS_SHARE come from global memory."""
+    return "A" if entries <= ALL_STAGED else "B" if entries <= LDS_SHARE else "C"
+
+
+def table_regime(f):
+    """-> dict(blocks=[Th0 DC, Th0 AC, Th1 DC, Th1 AC], first=[each table's first L2 entry], entries, regime)."""
+    blocks = [l2_blocks(f.huff[t]) for t in range(4)]
+    first = [L2_BLOCK * sum(blocks[:t]) for t in range(4)]
+    entries = L2_BLOCK * sum(blocks)
+    return dict(blocks=blocks, first=first, entries=entries, regime=regime_of(entries))
+
+
+def entry_of(f, t, symbol):
+    """The L2 entry index of the symbol's code in table slot t (its first, where the code is shorter than 16 bits); None
+    for a code of at most 8 bits."""
+    codes = canonical(f.huff[t])[2]
+    code, n = codes[symbol]
+    if n <= 8:
+        return None
+    prefixes = sorted({c >> (m - 8) for (c, m) in codes.values() if m > 8})
+    return table_regime(f)["first"][t] + L2_BLOCK * prefixes.index(code >> (n - 8)) + ((code << (16 - n)) & 0xFF)
+
+
+# kind -> (blocks up to the end of Th0 AC, blocks in all).  The DC tables hold categories 0..15 only (a higher one closes
+# the cooperative kernel and the walk: desc.cpp, fill_coop / mcu_ok), so they come to 4 blocks each or fewer and the AC
+# tables make up the rest.
+WIDE_KINDS = {
+    "wide_a": (16, 32),      # 8192 entries: the last file of regime A
+    "wide_b": (18, 36),      # 9216: the direct tables staged in part
+    "wide_b48": (24, 48),    # 12288: the last file of regime B -- L2 fills the share, nothing of the direct tables
+    "wide_c": (48, 92),      # Th0 AC ends at entry 12288: wholly staged; Th1 DC and Th1 AC wholly beyond
+    "wide_c2": (64, 88),     # entry 12288 lies inside Th0 AC: one table read from both places
+    "full": (64, 128),       # 32768 entries: the last file the parser accepts
+    "over": (64, 129),       # one block more: refused
+}
+_DC_BLOCKS = 4
+_TAIL = (10, 11, 12, 13, 14, 15, 16)
+
+
+def _wide_lengths(used, universe, n9):
+    """used symbols dealt in turn to four groups -- codes of at most 8 bits, the first of the 9-bit codes, the last of them,
+    a tail of one code each of 10 .. 16 bits -- and symbols the stream never uses filling the 9-bit codes up to n9 and the
+    tail up to seven.  canonical() keeps this order within a length: the used 9-bit codes stand at both ends of the
+    table's blocks, the tail in its last one.  None: the universe has too few symbols."""
+    used = list(dict.fromkeys(used))
+    spare = [s for s in universe if s not in used]
+    lo_cap = (n9 + 1) // 2
+    groups = {"short": [], "lo": [], "hi": [], "tail": []}
+    cap = {"short": len(used), "lo": lo_cap, "hi": n9 - lo_cap, "tail": len(_TAIL)}
+    turn = ["short", "lo", "hi", "tail"]
+    k = 0
+    for s in used:
+        while len(groups[turn[k % 4]]) >= cap[turn[k % 4]]:
+            k += 1
+        groups[turn[k % 4]].append(s)
+        k += 1
+    fill = n9 - len(groups["lo"]) - len(groups["hi"]) + len(_TAIL) - len(groups["tail"])
+    if fill > len(spare):
+        return None
+    pad9 = [spare.pop(0) for _ in range(n9 - len(groups["lo"]) - len(groups["hi"]))]
+    groups["tail"] += [spare.pop(0) for _ in range(len(_TAIL) - len(groups["tail"]))]
+    long_mass = n9 / 512 + sum(2.0 ** -n for n in _TAIL)
+    ns = next((n for n in range(1, 9) if len(groups["short"]) * 2.0 ** -n + long_mass < 1.0), None)
+    if ns is None:
+        return None
+    out = {s: ns for s in groups["short"]}
+    out.update({s: 9 for s in groups["lo"] + pad9 + groups["hi"]})
+    out.update(dict(zip(groups["tail"], _TAIL)))
+    return out
+
+
+def wide_table(used, universe, blocks):
+    """{symbol: length} over the used symbols and padding from `universe` with exactly `blocks` L2 blocks; with too few
+    symbols for that (a DC table of sixteen categories), as many as they make."""
+    best = None
+    for n9 in range(0, 2 * blocks + 1):
+        t = _wide_lengths(used, universe, n9)
+        if t is None:
+            break
+        best = t
+        if l2_blocks(t) == blocks:
+            return t
+    assert best is not None and universe is not _AC_UNIVERSE, (blocks, len(list(used)))
+    return best
+
+
+_AC_UNIVERSE = tuple(range(256))
+_DC_UNIVERSE = tuple(range(16))
+
+
+def wide_table_set(kind, dc_symbols, ac_symbols):
+    th0_end, total = WIDE_KINDS[kind]
+    dc0 = wide_table(dc_symbols, _DC_UNIVERSE, _DC_BLOCKS)
+    ac0 = wide_table(ac_symbols, _AC_UNIVERSE, th0_end - l2_blocks(dc0))
+    dc1 = dict(dc0)
+    ac1 = wide_table(ac_symbols, _AC_UNIVERSE, total - th0_end - l2_blocks(dc1))
+    return {0: dc0, 1: ac0, 2: dc1, 3: ac1}
 
 
 def symbols_of(dus):
@@ -557,9 +678,11 @@ def _ends(size):
     return (lo, -lo, hi, -hi)
 
 
-def ac_sizes(tables, layout="422"):
+def ac_sizes(tables, layout="422", dc=False):
     """Every size 1..15 at both ends of both signs, behind runs of 0 and of 15 (positions 1, 17 and 18; the all-ones
-    magnitudes fill the stream with stuffed FF bytes).  In `long` the symbol 0xFF is 16 + 15 = 31 bits."""
+    magnitudes fill the stream with stuffed FF bytes).  In `long` the symbol 0xFF is 16 + 15 = 31 bits.  dc: DC
+    differences of up to +-90 in place of zeros (a decode that loses its place in the stream then shows in the DC terms
+    too, which is all a 1/8-scale decode keeps)."""
     dus = []
     for size in range(1, 16):
         a, b, c, d = _ends(size)
@@ -567,7 +690,9 @@ def ac_sizes(tables, layout="422"):
         dus.append((0, [ac(15, d), ac(0, c), ac(15, a), EOB]))     # (the third lands on 33: dropped)
         dus.append((0, [ac(0, b), ac(0, d), ac(15, c), EOB]))
         dus.append((0, [ac(15, c), ac(15, d), EOB]))
-    return _frame("ac_sizes", tables, layout, dus)
+    if dc:
+        dus = [((37 * k) % 181 - 90, syms) for k, (_, syms) in enumerate(dus)]
+    return _frame("ac_sizes", tables, layout, dus, tag="_dc" if dc else "")
 
 
 def dc_cats(tables, layout="422", ri=1):
@@ -737,7 +862,7 @@ def dc_wrap(layout="422"):
 _ALL_AC = [r << 4 | s for r in range(16) for s in range(1, 16)] + [0x00, 0xF0]
 
 
-def random_dense(ri, layout="422", mcus=None, across=None, tag=""):
+def random_dense(ri, layout="422", mcus=None, across=None, tag="", tables="long"):
     """Seeded random symbol lists over the full symbol set of `long` (sizes 1..15, every run, ZRL, EOB).  With a DRI the
     reference's reader runs dry at some DC code of most intervals (quirk Q1: 16-bit codes all round); without one (a
     single interval) every DC category is kept to the bits the reader holds there, so that the whole frame decodes."""
@@ -745,13 +870,15 @@ def random_dense(ri, layout="422", mcus=None, across=None, tag=""):
     across = across or (7 if ri in (3, 7) else 8)
     rng = np.random.default_rng(1000 + ri + mcus)
     dpm = LAYOUTS[layout][0] * LAYOUTS[layout][1] + 2
+    huff = table_set(tables, range(16), _ALL_AC)
     dus = []
     left = 32
-    for _ in range(mcus * dpm):
+    for i in range(mcus * dpm):
+        dcl, acl = (huff[0], huff[1]) if i % dpm < dpm - 2 else (huff[2], huff[3])   # (Frame.sel: luma on Th0, chroma on Th1)
         size = int(rng.integers(0, 16))
-        if not ri:
-            size = min(size, left - 16)
-        left -= 16 + size
+        while not ri and size and dcl[size] + size > left:
+            size -= 1
+        left -= dcl[size] + size
         diff = extend(int(rng.integers(0, 1 << size)), size) if size else 0
         syms, pos = [], 1
         for _ in range(int(rng.integers(0, 24))):
@@ -768,13 +895,12 @@ def random_dense(ri, layout="422", mcus=None, across=None, tag=""):
                 break
         if pos < 64:
             syms.append(EOB)
-        for (_, s, _) in syms:
+        for (r, s, _) in syms:
             left += 32 if left < 32 else 0
-            left -= 16 + s
+            left -= acl[r << 4 | s] + s
         dus.append((diff, syms))
-    huff = table_set("long", range(16), _ALL_AC)
     qt = (np.arange(64) % 13 + 1, np.arange(64) % 7 + 2)
-    return _frame("random_dense", "long", layout, dus, ri=ri, fit=False, across=across, huff=huff, tag=tag, quant=qt)
+    return _frame("random_dense", tables, layout, dus, ri=ri, fit=False, across=across, huff=huff, tag=tag, quant=qt)
 
 
 def texture(layout="422"):
@@ -824,6 +950,48 @@ def cancel(layout="422", ri=1):
 def random_strip():
     """The `random_dense` strip of 520 MCUs without DRI (tests/route_matrix.py: STRIP_MCUS)."""
     return random_dense(0, mcus=520, across=1, tag="_strip")
+
+
+def one_mcu(tables, layout="422"):
+    """A frame of one MCU: a dozen different AC symbols in every data unit, so that each table's used codes are of every
+    length the table set has."""
+    dpm = LAYOUTS[layout][0] * LAYOUTS[layout][1] + 2
+    dus = [(97 * k - 150, [ac((k + j) % 3, (-1) ** j * ((1 << (j % 9)) + k)) for j in range(12)] + [EOB]) for k in range(dpm)]
+    return _frame("one_mcu", tables, layout, dus, fit=False)
+
+
+_WIDE = None
+
+
+def wide_cases():
+    """Frames whose Huffman tables outgrow their share of LDS (WIDE_KINDS; table_regime), in every layout: `ac_sizes`
+    without DRI, with DC differences -- its data units are those of its `short` twin, one frame per regime --, `dc_cats` at DRI 1 (64 intervals;
+    DC codes of 10 to 16 bits, which escape the cooperative kernel's direct DC table), `positions` under standard entropy,
+    `random_dense` at DRI 1 over 65 MCUs (two waves, every AC symbol in use: lookups all over the tables), a frame of one
+    MCU, and in 4:2:2 the dense strip of 520 MCUs.  Not part of cases(): tests/test_gpu_coef.py pins a kernel to each of
+    those."""
+    global _WIDE
+    if _WIDE is None:
+        out = []
+        for lay in LAYOUTS:
+            out += [ac_sizes(k, lay, dc=True) for k in ("wide_a", "wide_b", "wide_b48", "wide_c", "full")]
+            out += [dc_cats(k, lay) for k in ("wide_b", "wide_c", "wide_c2")]
+            out += [positions(k, True, lay) for k in ("wide_b", "wide_c")]
+            out += [random_dense(1, lay, mcus=65, across=5, tables=k) for k in ("wide_b", "wide_b48", "wide_c", "wide_c2", "full")]
+            out += [one_mcu(k, lay) for k in ("wide_c", "wide_c2")]
+        out.append(random_dense(0, mcus=520, across=1, tag="_strip", tables="wide_c"))
+        assert len({f.name for f in out}) == len(out)
+        _WIDE = out
+    return _WIDE
+
+
+def wide_case(name):
+    return next(f for f in wide_cases() if f.name == name)
+
+
+def one_block_too_many(layout="422"):
+    """`ac_sizes` under tables of 129 blocks: one more than `full`, the first file both parsers refuse."""
+    return ac_sizes("over", layout, dc=True)
 
 
 _CASES = None

@@ -208,7 +208,17 @@ int emul_decode(const uint8_t *jpeg, size_t len, uint8_t *rgba, uint32_t tex_w, 
         const uint32_t nrows = window_words ? window_words : 16u;
         const uint32_t stage_below = getenv("EMUL_STREAM_BELOW") ? uint32_t(strtoul(getenv("EMUL_STREAM_BELOW"), nullptr, 0)) : nrows / 2u;
         const bool with_tables = !(getenv("EMUL_WALK_TABLES") && atoi(getenv("EMUL_WALK_TABLES")) == 0);
-        const uint32_t l2n = (uint32_t(l2.size()) + 1u) & ~1u; // (everything staged: L2, direct AC and DC tables)
+        // As the runtime has it: the route is closed to tables that outgrow the LDS share (runtime.cpp: walk_luts_fit), and
+        // plan_walk stages the share's entries and the direct DC tables -- with tables that fit, everything: L2, direct AC
+        // and DC tables.  EMUL_WALK_ANY_TABLES=1 (a control) walks other tables all the same, at plan_walk's budget: the walk
+        // then reads its direct tables from LDS it has not staged.
+        const uint32_t staged = uint32_t(((img->l2.size() + 1) & ~size_t(1)) + img->ac_fast.size()); // runtime.cpp: staged_lut_entries
+        if (staged > kLutLdsShare && !(getenv("EMUL_WALK_ANY_TABLES") && atoi(getenv("EMUL_WALK_ANY_TABLES")) != 0)) {
+            snprintf(err, errlen, "image does not qualify for the walk + lane-per-MCU route");
+            delete img;
+            return -5;
+        }
+        const uint32_t l2n = (std::min(staged, kLutLdsShare) + 2u * kDcFastEntries + 1u) & ~1u; // kernels.hip: plan_walk
         const uint32_t walk_off = (align16((kL1Entries + l2n) * 2u) + 31u) & ~31u;
         constexpr uint32_t kSpareRows = 3; // (kernels.hip: kWalkSpareRows)
         const uint32_t chunk = getenv("EMUL_WALK_CHUNK") ? uint32_t(std::max(1, std::min(int(kWalkMaxChunk), atoi(getenv("EMUL_WALK_CHUNK"))))) : 1u;

@@ -9,7 +9,7 @@
 // one after the other, each through decode_wave_cropped itself.  The destination lies between two runs of sentinel
 // bytes inside one block, pre-filled with 0xA5; the whole block is written out for the test to look at.
 //
-//   crop_driver decode in.jpg out.bin flags waves_per_block window_words format shift x y width height pitch total
+//   crop_driver decode in.jpg out.bin flags waves_per_block window_words format shift x y width height pitch total [luts [control]]
 //   crop_driver touch cases.txt
 //
 // flags: COMPEG_PARSE_*; format: COMPEG_CROP_*; shift: bytes the destination begins behind a 16-byte boundary; pitch,
@@ -18,6 +18,8 @@
 // found it by going through the interval's MCUs one by one -- and crop_reach must give that; then every rectangle of a
 // 5 x 4-MCU image at DRI 1 .. 21 and without DRI against the same search made here; and two mutants of crop_reach, which
 // must each disagree with the search somewhere.
+// luts, control: how many LUT entries are staged behind L1 and the control that ignores it (tests/emul/lut_budget.h);
+// default: what the planner stages, the direct AC tables counted.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -28,6 +30,7 @@
 #include "../../compeg_amd/csrc/device_types.h"
 #include "../../compeg_amd/csrc/front.h"
 #include "../../compeg_amd/csrc/scan.h"
+#include "../emul/lut_budget.h"
 
 namespace compeg {
 void fill_desc(const ImageData &img, ImageDesc &d);
@@ -66,8 +69,8 @@ static void run_wave(const ImageDesc &d, const HuffShared &sh, const CropTarget 
 
 static int decode(int argc, char **argv)
 {
-    if (argc != 15) {
-        fprintf(stderr, "usage: %s decode in.jpg out.bin flags waves window_words format shift x y width height pitch total\n", argv[0]);
+    if (argc < 15 || argc > 15 + 2) {
+        fprintf(stderr, "usage: %s decode in.jpg out.bin flags waves window_words format shift x y width height pitch total [luts [control]]\n", argv[0]);
         return 2;
     }
     FILE *f = fopen(argv[2], "rb");
@@ -140,7 +143,10 @@ static int decode(int argc, char **argv)
     d.out = nullptr; // (a cropped decode has no texture)
 
     const uint32_t hs = d.hsample[0], vs = img->components == 1 ? 0u : d.vsample[0];
-    const uint32_t l2_in_lds = uint32_t(std::min<size_t>((img->l2.size() + 1) & ~size_t(1), 12288)); // (plan_huffman)
+    const LutBudget luts(argc, argv, 15);
+    luts.apply(d);
+    const uint32_t l2_in_lds = luts.in_lds(*img);
+    luts.report(d, l2_in_lds);
     const uint32_t threads = waves_per_block * kWave;
     const uint32_t wave_area = align16(window_words * 4u) + kWave * kDuSlotBytes;
     const uint32_t lds_bytes = align16((kL1Entries + l2_in_lds) * 2u) + waves_per_block * wave_area;
@@ -150,8 +156,8 @@ static int decode(int argc, char **argv)
             skipped.workgroups++; // (before it stages anything)
             continue;
         }
-        uint8_t *smem = static_cast<uint8_t *>(aligned_alloc(16, align16(lds_bytes)));
-        memset(smem, 0xa5, lds_bytes); // LDS is not zero-initialised
+        uint8_t *smem = static_cast<uint8_t *>(aligned_alloc(16, align16(luts.alloc_bytes(lds_bytes))));
+        memset(smem, 0xa5, luts.alloc_bytes(lds_bytes)); // LDS is not zero-initialised
         uint16_t *sl1 = reinterpret_cast<uint16_t *>(smem);
         uint16_t *sl2 = sl1 + kL1Entries;
         uint8_t *wave_base = smem + align16((kL1Entries + l2_in_lds) * 2u);
@@ -171,7 +177,7 @@ static int decode(int argc, char **argv)
             wave_window(d, wave_first, window_words, wb, wl);
             for (uint32_t lane = 0; lane < uint32_t(kWave); lane++)
                 stage_window(d, win, wb, wl, lane);
-            HuffShared sh{sl1, sl2, umin(l2_in_lds, d.fast_off + 2u * kFastEntries), win, wb, wl, slots};
+            HuffShared sh{sl1, sl2, luts.l2_staged(d, l2_in_lds), win, wb, wl, slots};
             if (hs == 2 && vs == 1)
                 run_wave<2, 1>(d, sh, g, wave_first, skipped);
             else if (hs == 1 && vs == 1)

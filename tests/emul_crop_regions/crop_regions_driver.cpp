@@ -9,12 +9,15 @@
 // tests are made where the kernel makes them.  The destination lies between two runs of sentinel bytes inside one
 // block, pre-filled with 0xA5; the whole block is written out for the test to look at.
 //
-//   crop_regions_driver manifest.txt out.bin
+//   crop_regions_driver manifest.txt out.bin [luts [control]]
 //
 // manifest.txt: "format pitch slot_w slot_h slot_bytes shift window_words waves mutant images regions", then per image
 // "path flags", then per region "image x y width height dst_x dst_y".  pitch, slot_bytes: compeg_crop_regions_shape's.
 // shift: bytes the destination begins behind a 16-byte boundary.  mutant 1: every region decodes the first record's
 // rectangle; mutant 2: a region's slot is its rank inside its sampling group, not its index -- the test must catch both.
+// luts, control: how many LUT entries are staged behind L1 and the control that ignores it (tests/emul/lut_budget.h);
+// default: what the planner stages for the batch -- its largest image's, the direct AC tables counted -- while each image
+// stages its own.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -27,6 +30,7 @@
 #include "../../compeg_amd/csrc/device_types.h"
 #include "../../compeg_amd/csrc/front.h"
 #include "../../compeg_amd/csrc/scan.h"
+#include "../emul/lut_budget.h"
 
 namespace compeg {
 void fill_desc(const ImageData &img, ImageDesc &d);
@@ -52,7 +56,7 @@ struct Image {
     }
 };
 
-static bool load(const char *path, unsigned flags, Image &out, ImageDesc &d)
+static bool load(const char *path, unsigned flags, const LutBudget &luts, Image &out, ImageDesc &d)
 {
     FILE *f = fopen(path, "rb");
     if (!f)
@@ -80,6 +84,7 @@ static bool load(const char *path, unsigned flags, Image &out, ImageDesc &d)
         return false;
     }
     fill_desc(*img, d);
+    luts.apply(d);
     out.words.assign(scan.words(), scan.words() + scan.nwords());
     out.starts.assign(scan.starts(), scan.starts() + scan.nstarts());
     out.l1.assign(img->l1, img->l1 + 1024);
@@ -89,7 +94,7 @@ static bool load(const char *path, unsigned flags, Image &out, ImageDesc &d)
         out.l2.push_back(0);
     out.l2.insert(out.l2.end(), img->ac_fast.begin(), img->ac_fast.end());
     out.l2.insert(out.l2.end(), img->dc_fast.begin(), img->dc_fast.end());
-    out.l2_in_lds = uint32_t(std::min<size_t>((img->l2.size() + 1) & ~size_t(1), 12288)); // (plan_huffman)
+    out.l2_in_lds = luts.in_lds(*img);
     out.hs = d.hsample[0];
     out.vs = img->components == 1 ? 0u : d.vsample[0];
     d.words = out.words.data();
@@ -109,7 +114,7 @@ struct Counts {
 // A row of the grid: the kernel's body for record `y` of the launch, every workgroup of the x extent.
 template <int HS, int VS>
 static void run_row(const ImageDesc *descs, const CropRegionRecord *records, uint32_t y, const CropRegionsTarget &t, uint32_t max_intervals,
-                    uint32_t l2_in_lds, uint32_t window_words, uint32_t waves_per_block, Counts &n)
+                    uint32_t l2_in_lds, uint32_t window_words, uint32_t waves_per_block, Counts &n, const LutBudget &luts)
 {
     const CropRegionRecord &r = records[y];
     const CropTarget g = crop_region_rect(r, t);
@@ -124,8 +129,8 @@ static void run_row(const ImageDesc *descs, const CropRegionRecord *records, uin
             n.workgroups_skipped++; // (before it stages anything)
             continue;
         }
-        uint8_t *smem = static_cast<uint8_t *>(aligned_alloc(16, align16(lds_bytes)));
-        memset(smem, 0xa5, lds_bytes); // LDS is not zero-initialised
+        uint8_t *smem = static_cast<uint8_t *>(aligned_alloc(16, align16(luts.alloc_bytes(lds_bytes))));
+        memset(smem, 0xa5, luts.alloc_bytes(lds_bytes)); // LDS is not zero-initialised
         uint16_t *sl1 = reinterpret_cast<uint16_t *>(smem);
         uint16_t *sl2 = sl1 + kL1Entries;
         uint8_t *wave_base = smem + align16((kL1Entries + l2_in_lds) * 2u);
@@ -145,7 +150,7 @@ static void run_row(const ImageDesc *descs, const CropRegionRecord *records, uin
             wave_window(d, wave_first, window_words, wb, wl);
             for (uint32_t lane = 0; lane < uint32_t(kWave); lane++)
                 stage_window(d, win, wb, wl, lane);
-            HuffShared sh{sl1, sl2, umin(l2_in_lds, d.fast_off + 2u * kFastEntries), win, wb, wl, slots};
+            HuffShared sh{sl1, sl2, luts.l2_staged(d, l2_in_lds), win, wb, wl, slots};
             for (uint32_t lane = 0; lane < uint32_t(kWave); lane++) {
                 decode_wave_cropped_region<HS, VS>(d, sh, g, t, wave_first + lane, lane);
                 n.lanes_walked += wave_first + lane < d.total_intervals && crop_intervals_reach(d, g, wave_first + lane, 1u) != 0u ? 1u : 0u;
@@ -157,10 +162,11 @@ static void run_row(const ImageDesc *descs, const CropRegionRecord *records, uin
 
 int main(int argc, char **argv)
 {
-    if (argc != 3) {
-        fprintf(stderr, "usage: %s manifest.txt out.bin\n", argv[0]);
+    if (argc < 3 || argc > 3 + 2) {
+        fprintf(stderr, "usage: %s manifest.txt out.bin [luts [control]]\n", argv[0]);
         return 2;
     }
+    const LutBudget luts(argc, argv, 3);
     FILE *m = fopen(argv[1], "r");
     if (!m)
         return 2;
@@ -177,10 +183,12 @@ int main(int argc, char **argv)
     for (unsigned i = 0; i < nimages; i++) {
         char path[4096];
         unsigned flags;
-        if (fscanf(m, "%4095s %u", path, &flags) != 2 || !load(path, flags, images[i], descs[i]))
+        if (fscanf(m, "%4095s %u", path, &flags) != 2 || !load(path, flags, luts, images[i], descs[i]))
             return 1;
         max_l2 = std::max(max_l2, images[i].l2_in_lds); // (plan_huffman: the batch's own maximum)
     }
+    for (unsigned i = 0; i < nimages; i++)
+        luts.report(descs[i], max_l2);
     std::vector<CropRegionPlace> places(nregions);
     for (unsigned k = 0; k < nregions; k++) {
         CropRegionPlace &p = places[k];
@@ -234,11 +242,11 @@ int main(int argc, char **argv)
         counts.launches += n ? 1u : 0u;
         for (uint32_t y = 0; y < n; y++) {
             switch (g) {
-            case 0: run_row<2, 1>(descs, group_records, y, call.target, call.intervals[g], max_l2, window_words, waves, counts); break;
-            case 1: run_row<1, 1>(descs, group_records, y, call.target, call.intervals[g], max_l2, window_words, waves, counts); break;
-            case 2: run_row<1, 2>(descs, group_records, y, call.target, call.intervals[g], max_l2, window_words, waves, counts); break;
-            case 3: run_row<2, 2>(descs, group_records, y, call.target, call.intervals[g], max_l2, window_words, waves, counts); break;
-            default: run_row<1, 0>(descs, group_records, y, call.target, call.intervals[g], max_l2, window_words, waves, counts); break;
+            case 0: run_row<2, 1>(descs, group_records, y, call.target, call.intervals[g], max_l2, window_words, waves, counts, luts); break;
+            case 1: run_row<1, 1>(descs, group_records, y, call.target, call.intervals[g], max_l2, window_words, waves, counts, luts); break;
+            case 2: run_row<1, 2>(descs, group_records, y, call.target, call.intervals[g], max_l2, window_words, waves, counts, luts); break;
+            case 3: run_row<2, 2>(descs, group_records, y, call.target, call.intervals[g], max_l2, window_words, waves, counts, luts); break;
+            default: run_row<1, 0>(descs, group_records, y, call.target, call.intervals[g], max_l2, window_words, waves, counts, luts); break;
             }
         }
         group_records += n;

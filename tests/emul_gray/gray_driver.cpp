@@ -7,10 +7,12 @@
 // heap copies of the words, the start positions and the LUTs.  The output lies between two runs of sentinel bytes inside
 // one block; the whole block is written out for the test to look at.
 //
-//   gray_driver in.jpg out.bin flags waves_per_block window_words single tex_w tex_h pitch alloc_h
+//   gray_driver in.jpg out.bin flags waves_per_block window_words single tex_w tex_h pitch alloc_h [luts [control]]
 //
 // flags: COMPEG_PARSE_*; single: 1 = the single-MCU form whatever the restart interval (0: pairs from two MCUs an
 // interval on, as the runtime dispatches); pitch x alloc_h: what lies behind the output pointer (bytes x rows).
+// luts, control: how many LUT entries are staged behind L1 and the control that ignores it (tests/emul/lut_budget.h);
+// default: what the planner stages, the direct AC tables counted.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -21,6 +23,7 @@
 #include "../../compeg_amd/csrc/front.h"
 #include "../../compeg_amd/csrc/gray_body.h"
 #include "../../compeg_amd/csrc/scan.h"
+#include "../emul/lut_budget.h"
 
 namespace compeg {
 void fill_desc(const ImageData &img, ImageDesc &d);
@@ -103,8 +106,8 @@ static void run_wave(const ImageDesc &d, const HuffShared &sh, uint32_t wave_fir
 
 int main(int argc, char **argv)
 {
-    if (argc != 11) {
-        fprintf(stderr, "usage: %s in.jpg out.bin flags waves window_words single tex_w tex_h pitch alloc_h\n", argv[0]);
+    if (argc < 11 || argc > 11 + 2) {
+        fprintf(stderr, "usage: %s in.jpg out.bin flags waves window_words single tex_w tex_h pitch alloc_h [luts [control]]\n", argv[0]);
         return 2;
     }
     FILE *f = fopen(argv[1], "rb");
@@ -175,14 +178,17 @@ int main(int argc, char **argv)
     d.out_alloc_h = alloc_h;
     d.out_pitch = pitch;
 
-    const uint32_t l2_in_lds = uint32_t(std::min<size_t>((img->l2.size() + 1) & ~size_t(1), 12288)); // (plan_huffman)
+    const LutBudget luts(argc, argv, 11);
+    luts.apply(d);
+    const uint32_t l2_in_lds = luts.in_lds(*img);
+    luts.report(d, l2_in_lds);
     const uint32_t threads = waves_per_block * kWave;
     const uint32_t wave_area = align16(window_words * 4u) + kWave * kDuSlotBytes;
     const uint32_t lds_bytes = align16((kL1Entries + l2_in_lds) * 2u) + waves_per_block * wave_area;
     const bool pairs = !single && d.restart_interval >= 2u;
     for (uint32_t first = 0; first < d.total_intervals; first += threads) {
-        uint8_t *smem = static_cast<uint8_t *>(aligned_alloc(16, align16(lds_bytes)));
-        memset(smem, 0xa5, lds_bytes); // LDS is not zero-initialised
+        uint8_t *smem = static_cast<uint8_t *>(aligned_alloc(16, align16(luts.alloc_bytes(lds_bytes))));
+        memset(smem, 0xa5, luts.alloc_bytes(lds_bytes)); // LDS is not zero-initialised
         uint16_t *sl1 = reinterpret_cast<uint16_t *>(smem);
         uint16_t *sl2 = sl1 + kL1Entries;
         uint8_t *wave_base = smem + align16((kL1Entries + l2_in_lds) * 2u);
@@ -198,7 +204,7 @@ int main(int argc, char **argv)
             wave_window(d, wave_first, window_words, wb, wl);
             for (uint32_t lane = 0; lane < uint32_t(kWave); lane++)
                 stage_window(d, win, wb, wl, lane);
-            HuffShared sh{sl1, sl2, umin(l2_in_lds, d.fast_off + 2u * kFastEntries), win, wb, wl, slots};
+            HuffShared sh{sl1, sl2, luts.l2_staged(d, l2_in_lds), win, wb, wl, slots};
             if (pairs)
                 run_wave<2>(d, sh, wave_first);
             else

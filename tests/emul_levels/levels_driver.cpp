@@ -9,9 +9,11 @@
 // destination lies between two runs of sentinel bytes inside one block, pre-filled with 0xA5; the whole block is
 // written out for the test to look at.
 //
-//   levels_driver in.jpg out.bin flags waves_per_block window_words order total offset0 offset1 offset2 bw0 bw1 bw2 bh0 bh1 bh2
+//   levels_driver in.jpg out.bin flags waves_per_block window_words order total offset0 offset1 offset2 bw0 bw1 bw2 bh0 bh1 bh2 [luts [control]]
 //
 // flags: COMPEG_PARSE_*; order: COMPEG_LEVELS_*; the rest: compeg_levels_shape's answer for the one image.
+// luts, control: how many LUT entries are staged behind L1 and the control that ignores it (tests/emul/lut_budget.h);
+// default: what the planner stages, the direct AC tables counted.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -22,6 +24,7 @@
 #include "../../compeg_amd/csrc/front.h"
 #include "../../compeg_amd/csrc/levels_body.h"
 #include "../../compeg_amd/csrc/scan.h"
+#include "../emul/lut_budget.h"
 
 namespace compeg {
 void fill_desc(const ImageData &img, ImageDesc &d);
@@ -68,8 +71,8 @@ static void run_wave(const ImageDesc &d, const HuffShared &sh, const LevelsTarge
 
 int main(int argc, char **argv)
 {
-    if (argc != 17) {
-        fprintf(stderr, "usage: %s in.jpg out.bin flags waves window_words order total offset[3] blocks_w[3] blocks_h[3]\n", argv[0]);
+    if (argc < 17 || argc > 17 + 2) {
+        fprintf(stderr, "usage: %s in.jpg out.bin flags waves window_words order total offset[3] blocks_w[3] blocks_h[3] [luts [control]]\n", argv[0]);
         return 2;
     }
     FILE *f = fopen(argv[1], "rb");
@@ -137,13 +140,16 @@ int main(int argc, char **argv)
     d.out = nullptr; // (a levels decode has no texture)
 
     const uint32_t hs = d.hsample[0], vs = img->components == 1 ? 0u : d.vsample[0];
-    const uint32_t l2_in_lds = uint32_t(std::min<size_t>((img->l2.size() + 1) & ~size_t(1), 12288)); // (plan_huffman)
+    const LutBudget luts(argc, argv, 17);
+    luts.apply(d);
+    const uint32_t l2_in_lds = luts.in_lds(*img);
+    luts.report(d, l2_in_lds);
     const uint32_t threads = waves_per_block * kWave;
     const uint32_t wave_area = align16(window_words * 4u) + kWave * kLevelsSlotBytes;
     const uint32_t lds_bytes = align16((kL1Entries + l2_in_lds) * 2u) + waves_per_block * wave_area;
     for (uint32_t first = 0; first < d.total_intervals; first += threads) {
-        uint8_t *smem = static_cast<uint8_t *>(aligned_alloc(16, align16(lds_bytes)));
-        memset(smem, 0xa5, lds_bytes); // LDS is not zero-initialised
+        uint8_t *smem = static_cast<uint8_t *>(aligned_alloc(16, align16(luts.alloc_bytes(lds_bytes))));
+        memset(smem, 0xa5, luts.alloc_bytes(lds_bytes)); // LDS is not zero-initialised
         uint16_t *sl1 = reinterpret_cast<uint16_t *>(smem);
         uint16_t *sl2 = sl1 + kL1Entries;
         uint8_t *wave_base = smem + align16((kL1Entries + l2_in_lds) * 2u);
@@ -159,7 +165,7 @@ int main(int argc, char **argv)
             wave_window(d, wave_first, window_words, wb, wl);
             for (uint32_t lane = 0; lane < uint32_t(kWave); lane++)
                 stage_window(d, win, wb, wl, lane);
-            HuffShared sh{sl1, sl2, umin(l2_in_lds, d.fast_off + 2u * kFastEntries), win, wb, wl, slots};
+            HuffShared sh{sl1, sl2, luts.l2_staged(d, l2_in_lds), win, wb, wl, slots};
             if (hs == 2 && vs == 1)
                 run_wave<2, 1>(d, sh, g, wave_first);
             else if (hs == 1 && vs == 1)

@@ -434,9 +434,37 @@ def ordering_decoder_decode_behind_stalled_regions():
     assert np.array_equal(dec.read_texture(48, 32), orc.ImageData(new.jpeg()).decode()), "the decode on the second stream did not decode its own frame"
 
 
+def tables_beyond_the_lds_share():
+    """Frames whose Huffman tables outgrow their share of LDS (cs.wide_cases, gs.wide_cases; cs.table_regime) in one batch, all
+    samplings and the three regimes side by side: a region of every image, so that every launch names regions of regime-A
+    and regime-C images -- planned with the largest image's tables while each image stages its own; chunks of 0, 1 and 7
+    regions, the three preprocessing modes.  And the Decoder's form on a regime-C frame of every sampling."""
+    import wide_emul as we
+    frames = [f for f in we.frames() if f.mcus <= 65]
+    for lay in we.SAMPLINGS:
+        assert {we.regime(f) for f in frames if we.layout_of(f) == lay} == set("ABC"), lay
+    fulls = [crs.frame_rgba(f) for f in frames]
+    slot = (max(f.w for f in frames) + 1, max(f.h for f in frames) + 1)
+    regions = [(i, (0, 0, f.w, f.h) if i % 2 == 0 else (f.w // 3, f.h // 4, max(1, f.w // 2), max(1, f.h // 2)), (i % 2, i % 3 % 2)) for i, f in enumerate(frames)]
+    for mode in (0, 1, 2):
+        batch = _upload(frames, mode)
+        regions_case(batch, fulls, regions, slot, rgs.FORMATS[mode % 2], pitched=mode == 0, odd=mode == 1, chunk=(0, 1, 7)[mode], what=f"wide tables, mode {mode}")
+    dec = ca.Decoder(gpu)
+    for n, lay in enumerate(we.SAMPLINGS):
+        k, f = next((k, f) for k, f in enumerate(frames) if we.layout_of(f) == lay and we.regime(f) == "C" and f.intervals == 65)
+        mine = [(0, (0, 0, f.w, f.h)), (0, (f.w // 3, f.h // 4, max(1, f.w // 2), max(1, f.h // 2)), (1, 1))]
+        format = rgs.FORMATS[n % 2]
+        pitch, slot_bytes = _geometry(slot, format, n == 0)
+        dst = Dest(slot_bytes * 2, _shift(format, n % 2 == 1))
+        dec.set_device_preprocess(n % 2 == 1)
+        dec.decode_cropped_regions(ca.ImageData(f.jpeg(), **f.image_kw()), dst.range, mine, slot, format, pitch, blocking=True)
+        assert dec.last_kernel() == "cropped", f.name
+        _compare(dst.read(f.name), rgs.destination([fulls[k]], mine, slot, format, pitch, before=np.full(dst.total, PREFILL, dtype=np.uint8)), f"Decoder: {f.name}")
+
+
 CASES = {f"mixed_batch[mode {m}]": (mixed_batch, (m,)) for m in (0, 1, 2)}
 CASES.update({fn.__name__: (fn, ()) for fn in (identity_with_the_one_rectangle_decode, identity_with_the_cards_own_rgba, decoder_form,
-                                               one_region_and_none, rgba_decodes_and_a_pack_around, refusals_on_the_card,
+                                               one_region_and_none, rgba_decodes_and_a_pack_around, refusals_on_the_card, tables_beyond_the_lds_share,
                                                ordering_batch_regions_behind_a_stalled_decode, ordering_batch_decode_behind_stalled_regions,
                                                ordering_decoder_regions_behind_a_stalled_decode, ordering_decoder_decode_behind_stalled_regions)})
 

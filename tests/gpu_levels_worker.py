@@ -535,10 +535,28 @@ def ordering_decoder_decode_behind_a_stalled_levels():
     assert np.array_equal(dec.read_texture(48, 32), orc.ImageData(new.jpeg()).decode()), "the decode on the second stream did not decode its own frame"
 
 
+def tables_beyond_the_lds_share():
+    """Frames whose Huffman tables outgrow their share of LDS (cs.wide_cases, gs.wide_cases; cs.table_regime): every regime-B
+    and regime-C frame of every sampling through the Decoder -- the direct tables staged in part, L2 lookups from global
+    memory beyond entry 12288 --, and batches of images of one size whose regimes are A, B and C: planned with the largest
+    image's tables while each image stages its own."""
+    import wide_emul as we
+    for layout in we.SAMPLINGS:
+        dec = ca.Decoder(gpu)
+        for i, f in enumerate(x for x in we.frames((layout,)) if we.regime(x) != "A"):
+            levels = ls.frame_levels(f)
+            for k, order in enumerate(ls.ORDERS):
+                decoder_case(f, order, device=(i + k) % 2 == 1, levels=levels, dec=dec, blocking=(i + k) % 3 != 0)
+        for n, frames in enumerate(we.same_size_batches(layout)):
+            levels = [ls.frame_levels(f) for f in frames]
+            for k, order in enumerate(ls.ORDERS):
+                batch_case(frames, order, mode=(n + k) % 3, chunk=2 * k, levels=levels)
+
+
 CASES = {f"coefficient_families[{lay}]": (coefficient_families, (lay,)) for lay in LAYOUTS}
 CASES.update({fn.__name__: (fn, ()) for fn in (standard_entropy_in_every_layout, tiny_and_one_lane, interval_counts, undecoded_tail,
                                                interval_longer_than_the_window, golden_files, batches, decoder_state_is_untouched,
-                                               refusals_on_the_card, ordering_batch_levels_behind_a_stalled_decode,
+                                               refusals_on_the_card, tables_beyond_the_lds_share, ordering_batch_levels_behind_a_stalled_decode,
                                                ordering_batch_decode_behind_a_stalled_levels, ordering_decoder_levels_behind_a_stalled_decode,
                                                ordering_decoder_decode_behind_a_stalled_levels)})
 

@@ -406,9 +406,25 @@ def ordering_decoder():
     _compare(dst.read("ordering, decoder")[0], want, "ordering, decoder: the planes after the next decode")
 
 
+def tables_beyond_the_lds_share():
+    """Frames whose Huffman tables outgrow their share of LDS (cs.wide_cases, gs.wide_cases; cs.table_regime): every regime-B
+    and regime-C frame of every sampling through the Decoder -- the direct tables staged in part, L2 lookups from global
+    memory beyond entry 12288 --, and batches of images of one size whose regimes are A, B and C: planned with the largest
+    image's tables while each image stages its own."""
+    import wide_emul as we
+    for layout in we.SAMPLINGS:
+        dec = ca.Decoder(gpu)
+        for i, f in enumerate(x for x in we.frames((layout,)) if we.regime(x) != "A"):
+            format, chroma = FORMATS_OF[layout][i % len(FORMATS_OF[layout])]
+            decoder_case(f, format, chroma, pitched=i % 3 == 0, shift=i % 2, device=i % 4 == 1, planes=ps.frame_planes(f), dec=dec, blocking=i % 5 != 0)
+        for n, frames in enumerate(we.same_size_batches(layout)):
+            format, chroma = FORMATS_OF[layout][n % len(FORMATS_OF[layout])]
+            batch_case(frames, format, chroma, pitched=n == 0, shift=n, mode=n * 2, chunk=2, planes=[ps.frame_planes(f) for f in frames])
+
+
 CASES = {f"geometry_and_intervals[{lay}]": (geometry_and_intervals, (lay,)) for lay in ("422", "444", "440", "420", "gray")}
 CASES.update({fn.__name__: (fn, ()) for fn in (many_intervals, interval_longer_than_the_window, families_that_break_readers, formats_on_422,
-                                               consistency_with_the_rgba_decode, batches, refusals_on_the_card, ordering_batch, ordering_decoder)})
+                                               consistency_with_the_rgba_decode, batches, refusals_on_the_card, tables_beyond_the_lds_share, ordering_batch, ordering_decoder)})
 
 
 def main(out_path, only=""):

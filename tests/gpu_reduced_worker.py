@@ -478,9 +478,23 @@ def ordering_decoder_decode_behind_a_stalled_reduced():
     assert np.array_equal(dec.read_texture(48, 32), orc.ImageData(new.jpeg()).decode()), "the decode on the second stream did not decode its own frame"
 
 
+def tables_beyond_the_lds_share():
+    """Frames whose Huffman tables outgrow their share of LDS (cs.wide_cases, gs.wide_cases; cs.table_regime): every regime-B
+    and regime-C frame of every sampling through the Decoder -- the direct tables staged in part, L2 lookups from global
+    memory beyond entry 12288 --, and batches of images of one size whose regimes are A, B and C: planned with the largest
+    image's tables while each image stages its own."""
+    import wide_emul as we
+    for layout in we.SAMPLINGS:
+        dec = ca.Decoder(gpu)
+        for i, f in enumerate(x for x in we.frames((layout,)) if we.regime(x) != "A"):
+            decoder_case(f, rs.FORMATS[i % 2], pitched=i % 3 == 0, odd=i % 4 == 1, red=rs.frame_reduced(f), dec=dec, device=i % 2 == 1, blocking=i % 5 != 0)
+        for n, frames in enumerate(we.same_size_batches(layout)):
+            batch_case(frames, rs.FORMATS[n % 2], pitched=n == 0, mode=n * 2, chunk=2, reds=[rs.frame_reduced(f) for f in frames])
+
+
 CASES = {f"cut_edges_and_intervals[{lay}]": (cut_edges_and_intervals, (lay,)) for lay in ("422", "444", "440", "420", "gray")}
 CASES.update({fn.__name__: (fn, ()) for fn in (many_intervals, undecoded_tail, tiny_frames, interval_longer_than_the_window, coefficient_families,
-                                               golden_files, identity_with_the_cards_own_rgba, batches, refusals_on_the_card,
+                                               golden_files, identity_with_the_cards_own_rgba, batches, refusals_on_the_card, tables_beyond_the_lds_share,
                                                ordering_batch_reduced_behind_a_stalled_decode, ordering_batch_decode_behind_a_stalled_reduced,
                                                ordering_decoder_reduced_behind_a_stalled_decode, ordering_decoder_decode_behind_a_stalled_reduced)})
 

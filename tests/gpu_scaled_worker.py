@@ -554,10 +554,30 @@ def ordering_decoder_decode_behind_a_stalled_scaled(den):
     assert np.array_equal(dec.read_texture(48, 32), orc.ImageData(new.jpeg()).decode()), "the decode on the second stream did not decode its own frame"
 
 
+def tables_beyond_the_lds_share():
+    """Frames whose Huffman tables outgrow their share of LDS (cs.wide_cases, gs.wide_cases; cs.table_regime): every regime-B
+    and regime-C frame of every sampling through the Decoder -- the direct tables staged in part, L2 lookups from global
+    memory beyond entry 12288 --, and batches of images of one size whose regimes are A, B and C: planned with the largest
+    image's tables while each image stages its own."""
+    import wide_emul as we
+    for layout in we.SAMPLINGS:
+        dec = ca.Decoder(gpu)
+        n = 0   # (counts the decodes: format, pitch, alignment, preprocessing and blocking vary with it)
+        for f in (x for x in we.frames((layout,)) if we.regime(x) != "A"):
+            x = Expect(f)
+            for den in DENS:
+                n += 1
+                decoder_case(x, den, sc.FORMATS[n % 2], pitched=n % 3 == 0, odd=n % 4 == 1, dec=dec, device=n % 2 == 1, blocking=n % 5 != 0)
+        for n, frames in enumerate(we.same_size_batches(layout)):
+            xs = [Expect(f) for f in frames]
+            for den in DENS:
+                batch_case(xs, den, sc.FORMATS[(n + den // 4) % 2], pitched=n == 0, mode=(n + den // 2) % 3, chunk=2)
+
+
 CASES = {f"cut_edges_and_intervals[{lay}]": (cut_edges_and_intervals, (lay,)) for lay in ("422", "444", "440", "420", "gray")}
 CASES.update({fn.__name__: (fn, ()) for fn in (many_intervals, undecoded_tail, tiny_frames, interval_longer_than_the_window, coefficient_families,
                                                golden_files, dc_only_identity_with_the_cards_own_reduced, denominator_8_is_the_reduced_decode,
-                                               batches, refusals_on_the_card)})
+                                               batches, refusals_on_the_card, tables_beyond_the_lds_share)})
 CASES.update({f"{fn.__name__}[1/{den}]": (fn, (den,)) for fn in (ordering_batch_scaled_behind_a_stalled_decode, ordering_batch_decode_behind_a_stalled_scaled,
                                                                   ordering_decoder_scaled_behind_a_stalled_decode,
                                                                   ordering_decoder_decode_behind_a_stalled_scaled) for den in DENS})

@@ -300,3 +300,28 @@ def cases():
 
 def case(name):
     return next(f for f in cases() if f.name == name)
+
+
+_WIDE = None
+
+
+def on_th1(g):
+    """The frame with its one component on Th1's tables: in cs.WIDE_KINDS' `wide_c` those lie wholly beyond the LDS share.
+    (The tables of one set give a used symbol the same group of lengths in Th0 and Th1; what the reference's reader makes of
+    the other lengths is cs.predict's to say.)"""
+    td, ta, tq = g.sel[0]
+    return GrayFrame(g.name + "/th1", "gray", g.mcus_w, g.mcus_h, g.dus, g.huff, ri=g.ri, quant=g.quant, sel=((1, 1, tq),) * 3,
+                     standard=g.standard, family=g.family, tables=g.tables)
+
+
+def wide_cases():
+    """cs.wide_cases() at layout 444 through gray_of: the file keeps all four tables, so its regime is the 4:4:4 frame's.
+    In regimes A and B the component decodes with Th0's tables; in regime C with Th1's, which lie wholly beyond the LDS
+    share in every kind -- its DC lookups too, so that a decode which keeps the DC terms alone (1/8 scale) meets them."""
+    global _WIDE
+    if _WIDE is None:
+        out = [gray_of(f) for f in cs.wide_cases() if f.layout == "444"]
+        out = [on_th1(g) if cs.table_regime(g)["regime"] == "C" else g for g in out]
+        assert len({f.name for f in out}) == len(out)
+        _WIDE = out
+    return _WIDE

@@ -7,7 +7,16 @@ what the writer predicted.
 
 A route may say "does not qualify" only where must_not_qualify() says so: the cooperative kernel and the walk for
 `dc_hostile` (a DC category above 15: the direct tables cannot hold it), the cooperative kernel for the two strips
-(one interval of more than kCoopMaxRestart = 256 MCUs).  Everything else must run on every route."""
+(one interval of more than kCoopMaxRestart = 256 MCUs).  Everything else must run on every route.
+
+cs.wide_cases() -- Huffman tables that outgrow their share of LDS (cs.table_regime) -- run the same routes twice: with
+the entries the planners stage, min(staged_lut_entries, 12288) behind L1 (runtime.cpp, kernels.hip: plan_huffman), where
+regime B has the direct tables in part and regime C reads L2 from global memory beyond entry 12288, and with everything
+staged.  (The cooperative kernel stages all its tables whatever the budget, as plan_coop does.)  The walk + lane-per-MCU
+route stages what plan_walk stages -- the share's entries and the direct DC tables -- whatever `l2` is given, and
+refuses tables beyond the share as the dispatch does (runtime.cpp: walk_luts_fit): its walk reads the direct tables
+from LDS alone.  A control walks such tables all the same and must get wrong pixels: what the card showed before the
+dispatch kept them off the route."""
 import numpy as np
 import pytest
 
@@ -16,6 +25,7 @@ from oracle import oracle as orc
 from test_kernel_emulation import STATS, _run, runner  # noqa: F401  (the fixture builds tests/emul)
 
 NAMES = [f.name for f in cs.cases()]
+WIDE = [f.name for f in cs.wide_cases()]
 
 
 def must_not_qualify(f):
@@ -83,3 +93,51 @@ def test_emulated_routes_on_coefficient_frames(runner, tmp_path, name):
         if route in ("two_kernel", "split"):
             _check_records(f, tmp_path, pred, f"{name}: {what}")
     assert refused == must_not_qualify(f), f"{name}: refused by {sorted(refused)}, expected {sorted(must_not_qualify(f))}"
+
+
+def staged_lut_entries(f):
+    """runtime.cpp: staged_lut_entries -- L2, padded to a dword, and the two direct AC tables."""
+    return (cs.table_regime(f)["entries"] + 1 & ~1) + 2 * cs.FAST_ENTRIES
+
+
+@pytest.mark.parametrize("name", WIDE)
+def test_emulated_routes_on_wide_table_frames(runner, tmp_path, name):
+    f = cs.wide_case(name)
+    want = orc.ImageData(f.jpeg(), **f.image_kw()).decode()
+    budgets = sorted({min(staged_lut_entries(f), cs.LDS_SHARE), staged_lut_entries(f)})
+    assert len(budgets) == (1 if cs.table_regime(f)["regime"] == "A" else 2)
+    for l2 in budgets:
+        refused = set()
+        for route, what, kw in _routes(f):
+            if route == "coop" and l2 != budgets[0]:
+                continue   # (the runner stages all of the cooperative kernel's tables: one run)
+            kept = dict(STATS)
+            try:
+                got = _run(runner, tmp_path, f.jpeg(), standard=f.standard, l2=l2, **kw)
+            finally:
+                STATS.clear()
+                STATS.update(kept)
+            if got is None:
+                refused.add(route)
+                continue
+            assert got.shape == want.shape and np.array_equal(got, want), \
+                f"{name}: {what}, {l2} entries staged: {int((got != want).any(axis=2).sum())} pixels differ"
+        expected = (must_not_qualify(f) | ({"walk"} if f.layout == "422" and cs.table_regime(f)["regime"] != "A" else set())) - (set() if l2 == budgets[0] else {"coop"})
+        assert refused == expected, f"{name}: refused by {sorted(refused)}, expected {sorted(expected)}"
+
+
+@pytest.mark.parametrize("name", ["positions/wide_b/422/standard/dri4", "positions/wide_c/422/standard/dri4", "random_dense_strip/wide_c/422/reference"])
+def test_the_walk_cannot_take_tables_beyond_the_lds_share(runner, tmp_path, name):
+    """Why walk_luts_fit exists: at plan_walk's budget the direct AC and DC tables of a regime-B or -C image are not (all)
+    in LDS, and the walk reads them nowhere else.  Walked all the same, these frames decode wrong -- as they did on the
+    card, through `walk_mcu`, before the dispatch kept them off the route; as the runtime runs it, the route refuses them."""
+    f = cs.wide_case(name)
+    want = orc.ImageData(f.jpeg(), **f.image_kw()).decode()
+    kept = dict(STATS)
+    try:
+        assert _run(runner, tmp_path, f.jpeg(), 8, window=40, below=20, standard=f.standard) is None
+        got = _run(runner, tmp_path, f.jpeg(), 8, window=40, below=20, standard=f.standard, walk_any_tables=True)
+    finally:
+        STATS.clear()
+        STATS.update(kept)
+    assert got is not None and got.shape == want.shape and not np.array_equal(got, want), f"{name}: the walk decodes it right without its direct tables"

@@ -21,6 +21,7 @@ import coef_stream as cs
 import crop_stream as crs
 import gray_stream as gs
 import planes_stream as ps
+import wide_emul as we
 from conftest import ROOT
 
 SENTINEL, PREFILL, GUARD = 0x5C, 0xA5, 256
@@ -40,7 +41,7 @@ def driver(tmp_path_factory):
     return exe
 
 
-def _run(driver, tmp_path, f, full, rect, format, destination, shift, window, waves=3):
+def _run(driver, tmp_path, f, full, rect, format, destination, shift, window, waves=3, luts=()):
     """-> the driver's counts: (skipped workgroups, waves, lanes, walked lanes, walked MCUs, stored MCUs)."""
     rgba, mask = full
     (tmp_path / "in.jpg").write_bytes(f.jpeg())
@@ -50,7 +51,8 @@ def _run(driver, tmp_path, f, full, rect, format, destination, shift, window, wa
     flags = (4 if comps == 1 else 1) | (2 if f.standard else 0)
     args = [driver, "decode", str(tmp_path / "in.jpg"), str(tmp_path / "out.bin"), str(flags), str(waves), str(window), str(crs.FORMATS.index(format)),
             str(shift)] + [str(v) for v in rect] + [str(pt), str(total)]
-    r = subprocess.run(args, capture_output=True, text=True, timeout=120)
+    r = subprocess.run(args + list(luts), capture_output=True, text=True, timeout=120)
+    we.note(r.stderr)
     what = f"{f.name}: {rect}, {format}, window {window}, {destination}, shift {shift}"
     assert r.returncode == 0 and r.stdout.startswith("ok "), what + "\n" + r.stdout[-500:] + r.stderr[-4000:]
     lines = r.stdout.splitlines()
@@ -61,6 +63,8 @@ def _run(driver, tmp_path, f, full, rect, format, destination, shift, window, wa
     got = block[GUARD + shift:-GUARD]
     want = crs.destination(rgba, mask, rect, format, pitch, before=np.full(total, PREFILL, dtype=np.uint8))
     bad = np.flatnonzero(got != want)
+    if "beyond" in luts:
+        return bad.size   # (the control: the caller says what it expects)
     assert not bad.size, f"{what}: {bad.size} bytes differ, first at {bad[0]}: {got[bad[0]]} != {want[bad[0]]}"
     return tuple(int(v) for v in re.findall(r"\d+", lines[1]))
 
@@ -159,3 +163,26 @@ def test_touch_test_against_the_search_and_its_mutants(driver, tmp_path):
     for which in ("listed", "exhaustive"):
         assert found[which][3] > 0, f"no {which} case catches the mutant that is off by one at the row wrap"
         assert found[which][4] > 0, f"no {which} case catches the mutant that ignores an interval's last MCU"
+
+
+@pytest.mark.parametrize("name", [f.name for f in we.frames()])
+def test_lane_body_on_tables_beyond_the_lds_share(driver, tmp_path, name):
+    """cs.wide_cases / gs.wide_cases at the planner's budget (tests/emul/lut_budget.h): regime B with the direct tables staged
+    in part and the fast mode off, regime C with L2 lookups from global memory beyond entry 12288 -- the driver reports
+    what it staged -- and the control: told that everything is staged, every regime-C frame differs from its expectation."""
+    f = we.frame(name)
+    full = crs.frame_rgba(f)
+    whole = (0, 0, f.w, f.h)
+    inner = (f.w // 3, f.h // 4, max(1, f.w // 2), max(1, f.h // 2))
+    _run(driver, tmp_path, f, full, whole, "rgba", "pitched", 4, 8, luts=we.PLAN)
+    we.check_plan(f)
+    _run(driver, tmp_path, f, full, inner, "rgb_planar", "tight", 1, 300, luts=we.PLAN)
+    if we.regime(f) == "C":
+        we.check_control(f, _run(driver, tmp_path, f, full, whole, "rgba", "pitched", 4, 8, luts=we.BEYOND))
+
+
+def test_ordinary_tables_decode_in_the_fast_mode(driver, tmp_path):
+    f = cs.case("random_dense/long/422/reference/dri3")
+    _run(driver, tmp_path, f, crs.frame_rgba(f), (0, 0, f.w, f.h), "rgba", "tight", 0, 300)
+    l2 = cs.table_regime(f)["entries"]
+    assert we.REPORTS == [(l2 + 2 * cs.FAST_ENTRIES, l2 + 2 * cs.FAST_ENTRIES, 1)]

@@ -17,6 +17,7 @@ import pytest
 import compeg_amd as ca   # (the host front end, for the short frame's expectation: no device is opened)
 import crop_regions_stream as rgs
 import planes_stream as ps
+import wide_emul as we
 from conftest import ROOT
 
 SENTINEL, PREFILL, GUARD = 0x5C, 0xA5, 256
@@ -49,7 +50,7 @@ def batch(tmp_path_factory):
     return frames, fulls, paths
 
 
-def _run(driver, tmp_path, batch, regions, format, destination, shift, window, waves=3, mutant=0):
+def _run(driver, tmp_path, batch, regions, format, destination, shift, window, waves=3, mutant=0, luts=()):
     """-> (bytes differing from the expectation, the driver's group counts)."""
     frames, fulls, paths = batch
     slot = rgs.SLOT
@@ -62,7 +63,8 @@ def _run(driver, tmp_path, batch, regions, format, destination, shift, window, w
             fh.write(f"{path} {(4 if comps == 1 else 1) | (2 if f.standard else 0)}\n")
         for image, rect, place in regions:
             fh.write(f"{image} {rect[0]} {rect[1]} {rect[2]} {rect[3]} {place[0]} {place[1]}\n")
-    r = subprocess.run([driver, str(tmp_path / "manifest.txt"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([driver, str(tmp_path / "manifest.txt"), str(tmp_path / "out.bin")] + list(luts), capture_output=True, text=True, timeout=300)
+    we.note(r.stderr)
     what = f"{format}, window {window}, {destination}, shift {shift}, mutant {mutant}"
     assert r.returncode == 0 and r.stdout.startswith("ok "), what + "\n" + r.stdout[-500:] + r.stderr[-4000:]
     total = slot_bytes * len(regions)
@@ -100,3 +102,43 @@ def test_the_mutants_are_caught(driver, tmp_path, batch, mutant):
     """1: the first record's rectangle for every region; 2: slot k placed by the region's rank inside its sampling group."""
     bad, _, _, _, _, what = _run(driver, tmp_path, batch, rgs.mixed_regions(), "rgba", "tight", 0, 300, mutant=mutant)
     assert bad.size, f"{what}: the mutant writes what the expectation has"
+
+
+@pytest.fixture(scope="module")
+def wide_batch(tmp_path_factory):
+    """Every wide frame of every sampling but the strip in one batch: regimes A, B and C side by side, planned with the
+    largest image's tables while each image stages its own (tests/emul/lut_budget.h)."""
+    import crop_stream as crs
+    tmp = tmp_path_factory.mktemp("emul_crop_regions_wide")
+    frames = [(f, we.layout_of(f)) for f in we.frames() if f.mcus <= 65]
+    fulls = [crs.frame_rgba(f) for f, _ in frames]
+    paths = []
+    for i, (f, _) in enumerate(frames):
+        (tmp / f"{i}.jpg").write_bytes(f.jpeg())
+        paths.append(str(tmp / f"{i}.jpg"))
+    return frames, fulls, paths
+
+
+def test_regions_of_images_with_tables_beyond_the_lds_share(driver, tmp_path, wide_batch, monkeypatch):
+    """A region of every image -- the whole frame, or a rectangle inside it -- in one list: each launch names regions of
+    regime-A, -B and -C images.  Every byte; then the control: every regime-C image's slot differs, no other does."""
+    frames = wide_batch[0]
+    slot = (max(f.w for f, _ in frames) + 1, max(f.h for f, _ in frames) + 1)
+    monkeypatch.setattr(rgs, "SLOT", slot)
+    regions = [(i, (0, 0, f.w, f.h) if i % 2 == 0 else (f.w // 3, f.h // 4, max(1, f.w // 2), max(1, f.h // 2)), (i % 2, i % 3 % 2))
+               for i, (f, _) in enumerate(frames)]
+    for lay in rgs.GROUPS:
+        assert {we.regime(f) for f, l in frames if l == lay} == set("ABC"), lay
+    bad, groups, launches, got, want, what = _run(driver, tmp_path, wide_batch, regions, "rgba", "pitched", 4, 8, luts=we.PLAN)
+    assert not bad.size, f"{what}: {bad.size} bytes differ, first at {bad[0]}: {got[bad[0]]} != {want[bad[0]]}"
+    assert launches == 5 and sum(groups) == len(regions)
+    assert len(we.REPORTS) == len(frames) and {r[0] for r in we.REPORTS} == {12288}, "the batch is planned with its largest image's tables"
+    for (f, _), report in zip(frames, we.REPORTS):
+        assert report[1:] == we.planned(f)[1:] or we.regime(f) == "A", f.name
+        assert report[2] == we.fast_mode(f), f.name
+    bad, _, _, got, want, what = _run(driver, tmp_path, wide_batch, regions, "rgb_planar", "tight", 0, 300, luts=we.PLAN)
+    assert not bad.size, f"{what}: {bad.size} bytes differ, first at {bad[0]}"
+    bad, _, _, got, want, what = _run(driver, tmp_path, wide_batch, regions, "rgba", "pitched", 4, 8, luts=we.BEYOND)
+    differs = (got.reshape(len(regions), -1) != want.reshape(len(regions), -1)).any(axis=1)
+    for (f, _), d in zip(frames, differs):
+        assert d == (we.regime(f) == "C"), f"{f.name}: regime {we.regime(f)}, its slot {'differs' if d else 'does not differ'} under the control"

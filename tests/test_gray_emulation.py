@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import gray_stream as gs
+import wide_emul as we
 from conftest import ROOT
 from test_gray_stream import FIXTURES, fixture, pil_l
 
@@ -81,12 +82,13 @@ def _expected(f, tex_w, tex_h, pitch, rows):
     return out, either
 
 
-def _run(driver, tmp_path, f, jpeg, form, window, output):
+def _run(driver, tmp_path, f, jpeg, form, window, output, luts=()):
     (tmp_path / "in.jpg").write_bytes(jpeg)
     tex_w, tex_h, pitch, rows = _geometry(f, output)
     flags = 4 | (2 if f.standard else 0)
     r = subprocess.run([driver, str(tmp_path / "in.jpg"), str(tmp_path / "out.bin"), str(flags), "3", str(window), "1" if form == "single" else "0",
-                        str(tex_w), str(tex_h), str(pitch), str(rows)], capture_output=True, text=True, timeout=120)
+                        str(tex_w), str(tex_h), str(pitch), str(rows)] + list(luts), capture_output=True, text=True, timeout=120)
+    we.note(r.stderr)
     what = f"{f.name}: {form}, window {window}, {output}"
     assert r.returncode == 0 and r.stdout.startswith("ok "), what + "\n" + r.stdout[-500:] + r.stderr[-4000:]
     assert r.stdout.split()[1:] == [str(f.w), str(f.h), str(f.intervals), str(f.interval)], what
@@ -97,6 +99,8 @@ def _run(driver, tmp_path, f, jpeg, form, window, output):
     if output == "padded":
         either[:] = False   # (every MCU is stored whole there)
     bad = np.argwhere((got != want) & ~(either & (got == PREFILL)))
+    if "beyond" in luts:
+        return len(bad)   # (the control: the caller says what it expects)
     assert not bad.size, f"{what}: {len(bad)} bytes differ, first at row {bad[0][0]} byte {bad[0][1]}: {got[tuple(bad[0])]} != {want[tuple(bad[0])]}"
 
 
@@ -123,3 +127,29 @@ def test_lane_body_on_pil_files(driver, tmp_path, w, h, blocks):
     f = gs.from_jpeg(j)
     for form, window, output in VARIANTS:
         _run(driver, tmp_path, f, j, form, window, output)
+
+
+@pytest.mark.parametrize("name", [f.name for f in we.frames(("gray",))])
+def test_lane_body_on_tables_beyond_the_lds_share(driver, tmp_path, name):
+    """cs.wide_cases / gs.wide_cases at the planner's budget (tests/emul/lut_budget.h): regime B with the direct tables staged
+    in part and the fast mode off, regime C with L2 lookups from global memory beyond entry 12288 -- the driver reports
+    what it staged -- and the control: told that everything is staged, every regime-C frame differs from its expectation."""
+    f = we.frame(name)
+    for form, window, output in VARIANTS:
+        if form == "single" and f.interval == 1 and output != "padded":
+            continue
+        _run(driver, tmp_path, f, f.jpeg(), form, window, output, luts=we.PLAN)
+        we.check_plan(f)
+    if we.regime(f) == "C":
+        form, window, output = VARIANTS[0]
+        we.check_control(f, _run(driver, tmp_path, f, f.jpeg(), form, window, output, luts=we.BEYOND))
+
+
+def test_ordinary_tables_are_staged_with_their_direct_tables(driver, tmp_path):
+    """The planner's budget counts the direct AC tables (runtime.cpp: staged_lut_entries) and the body is told so.  The fast
+    entropy mode stays off all the same: a grayscale image's absent components name no direct table (we.fast_mode)."""
+    import coef_stream as cs
+    f = FRAMES[0]
+    _run(driver, tmp_path, f, f.jpeg(), *VARIANTS[0])
+    l2 = cs.table_regime(f)["entries"]
+    assert we.REPORTS == [(l2 + 2 * cs.FAST_ENTRIES, l2 + 2 * cs.FAST_ENTRIES, 0)]

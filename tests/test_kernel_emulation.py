@@ -32,7 +32,7 @@ STATS = {}   # rare-path counters of the emulated kernels, summed over every run
 
 
 def _run(runner, tmp_path, jpeg, fused, waves=1, window=2048, l2=12288, standard=False, coop_passes=1, stage=8, below=None,
-         layout_rows=None, chunk=1, padded=False, singles=False):
+         layout_rows=None, chunk=1, padded=False, singles=False, walk_any_tables=False):
     p = tmp_path / "in.jpg"
     p.write_bytes(jpeg)
     env = dict(os.environ)
@@ -46,6 +46,9 @@ def _run(runner, tmp_path, jpeg, fused, waves=1, window=2048, l2=12288, standard
     env.pop("EMUL_STREAM_ROWS", None)
     env["EMUL_WALK_CHUNK"] = str(chunk)   # (fused = 8: MCUs a lane walks between two looks at what it found)
     env.pop("EMUL_SINGLES", None)
+    env.pop("EMUL_WALK_ANY_TABLES", None)
+    if walk_any_tables:
+        env["EMUL_WALK_ANY_TABLES"] = "1"   # (fused = 8, a control: tables beyond the LDS share walked at plan_walk's budget, which the runtime never does)
     if singles:
         env["EMUL_SINGLES"] = "1"   # (fused = 6, 8-pixel MCUs: every odd restart interval through the single-MCU form -- the library's for intervals of one MCU)
     env["EMUL_PADDED"] = "1" if padded else "0"   # (the output as the runtime allocates it: rows of whole MCUs, 16 pixels each way)
@@ -64,7 +67,7 @@ def _run(runner, tmp_path, jpeg, fused, waves=1, window=2048, l2=12288, standard
     if fused == 5 and "does not qualify for the cooperative kernel" in r.stdout:
         return None   # (no restart interval of 1..256 MCUs, or tables the direct tables cannot hold)
     if fused == 8 and "does not qualify for the walk" in r.stdout:
-        return None   # (tables the direct tables cannot hold, a DC category above 15)
+        return None   # (tables the direct tables cannot hold, a DC category above 15; tables beyond the LDS share: walk_luts_fit)
     assert r.returncode == 0, r.stdout + r.stderr[-2000:]
     _, w, h, _ = r.stdout.split()
     for line in r.stderr.splitlines():

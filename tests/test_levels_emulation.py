@@ -16,6 +16,7 @@ import coef_stream as cs
 import gray_stream as gs
 import levels_stream as ls
 import planes_stream as ps
+import wide_emul as we
 from conftest import ROOT
 
 SENTINEL, PREFILL, GUARD = 0x5C, 0xA5, 256
@@ -48,7 +49,7 @@ def driver(tmp_path_factory):
     return exe
 
 
-def _run(driver, tmp_path, f, levels, order, window, waves):
+def _run(driver, tmp_path, f, levels, order, window, waves, luts=()):
     (tmp_path / "in.jpg").write_bytes(f.jpeg())
     mw, mh, comps, hs, vs = ls.frame_geometry(f)
     lay, total = ls.shape(f.w, f.h, comps, hs, vs)
@@ -56,7 +57,8 @@ def _run(driver, tmp_path, f, levels, order, window, waves):
     pad = [0] * (3 - comps)
     args = [driver, str(tmp_path / "in.jpg"), str(tmp_path / "out.bin"), str(flags), str(waves), str(window), str(ls.ORDERS.index(order)), str(total)]
     args += [str(x) for key in ("offset", "blocks_w", "blocks_h") for x in [c[key] for c in lay] + pad]
-    r = subprocess.run(args, capture_output=True, text=True, timeout=120)
+    r = subprocess.run(args + list(luts), capture_output=True, text=True, timeout=120)
+    we.note(r.stderr)
     what = f"{f.name}: {order}, window {window}, {waves} waves a workgroup"
     assert r.returncode == 0 and r.stdout.startswith("ok "), what + "\n" + r.stdout[-500:] + r.stderr[-4000:]
     assert r.stdout.split()[1:] == [str(f.w), str(f.h), str(f.intervals), str(f.interval)], what
@@ -66,6 +68,8 @@ def _run(driver, tmp_path, f, levels, order, window, waves):
     got = block[GUARD:-GUARD]
     want = ls.destination(levels, mw, mh, comps, hs, vs, order, before=np.full(total, PREFILL, dtype=np.uint8))
     bad = np.flatnonzero(got != want)
+    if "beyond" in luts:
+        return bad.size   # (the control: the caller says what it expects)
     assert not bad.size, f"{what}: {bad.size} bytes differ, first at {bad[0]}: {got[bad[0]]} != {want[bad[0]]}"
     return want
 
@@ -112,3 +116,26 @@ def test_the_families_reach_beyond_position_31():
     for layout in ("422", "444", "440", "420", "gray"):
         frames = [f for f in _family_frames() if ("/gray/" in f.name) == (layout == "gray") and (layout == "gray" or f.layout == layout)]
         assert any(ls.frame_levels(f)[:, 32:].any() for f in frames), layout
+
+
+@pytest.mark.parametrize("name", [f.name for f in we.frames()])
+def test_lane_body_on_tables_beyond_the_lds_share(driver, tmp_path, name):
+    """cs.wide_cases / gs.wide_cases at the planner's budget (tests/emul/lut_budget.h): regime B with the direct tables staged
+    in part and the fast mode off, regime C with L2 lookups from global memory beyond entry 12288 -- the driver reports
+    what it staged -- and the control: told that everything is staged, every regime-C frame differs from its expectation."""
+    f = we.frame(name)
+    levels = ls.frame_levels(f)
+    _run(driver, tmp_path, f, levels, "zigzag", 8, 2, luts=we.PLAN)
+    we.check_plan(f)
+    _run(driver, tmp_path, f, levels, "natural", 300, 3, luts=we.PLAN)
+    if we.regime(f) == "C":
+        we.check_control(f, _run(driver, tmp_path, f, levels, "natural", 300, 3, luts=we.BEYOND))
+
+
+def test_ordinary_tables_decode_in_the_fast_mode(driver, tmp_path):
+    """The planner's budget counts the direct AC tables (runtime.cpp: staged_lut_entries): with ordinary tables the body is
+    told they are staged and the fast entropy mode is on, as on the card."""
+    f = cs.case("texture/edge/422/reference/dri4")
+    _run(driver, tmp_path, f, ls.frame_levels(f), "zigzag", 300, 3)
+    l2 = cs.table_regime(f)["entries"]
+    assert we.REPORTS == [(l2 + 2 * cs.FAST_ENTRIES, l2 + 2 * cs.FAST_ENTRIES, 1)]

@@ -13,6 +13,7 @@ import pytest
 
 import coef_stream as cs
 import planes_stream as ps
+import wide_emul as we
 from conftest import ROOT
 
 SENTINEL, PREFILL, GUARD = 0x5C, 0x3C, 256
@@ -53,7 +54,7 @@ def _pitch(f, format, chroma, destination):
     return ((rows[0] + 15) // 16 * 16 + 16, (rows[-1] + 15) // 16 * 16 + 32 if len(rows) > 1 else 0)
 
 
-def _run(driver, tmp_path, f, planes, format, chroma, window, destination, shift):
+def _run(driver, tmp_path, f, planes, format, chroma, window, destination, shift, luts=()):
     (tmp_path / "in.jpg").write_bytes(f.jpeg())
     comps, hs, vs = ps.sampling_of(f)
     pitch = _pitch(f, format, chroma, destination)
@@ -63,7 +64,8 @@ def _run(driver, tmp_path, f, planes, format, chroma, window, destination, shift
             "1" if chroma == "420" else "0", str(shift), str(total), str(len(lay))]
     for off, pt, row, _, rows in lay:
         args += [str(off), str(pt), str(row), str(rows)]
-    r = subprocess.run(args, capture_output=True, text=True, timeout=120)
+    r = subprocess.run(args + list(luts), capture_output=True, text=True, timeout=120)
+    we.note(r.stderr)
     what = f"{f.name}: {format}/{chroma}, window {window}, {destination}, shift {shift}"
     assert r.returncode == 0 and r.stdout.startswith("ok "), what + "\n" + r.stdout[-500:] + r.stderr[-4000:]
     assert r.stdout.split()[1:] == [str(f.w), str(f.h), str(f.intervals), str(f.interval)], what
@@ -73,6 +75,8 @@ def _run(driver, tmp_path, f, planes, format, chroma, window, destination, shift
     got = block[GUARD + shift:-GUARD]
     want = ps.destination(planes, f.w, f.h, comps, hs, vs, format, chroma, pitch, before=np.full(total, PREFILL, dtype=np.uint8))
     bad = np.flatnonzero(got != want)
+    if "beyond" in luts:
+        return bad.size   # (the control: the caller says what it expects)
     assert not bad.size, f"{what}: {bad.size} bytes differ, first at {bad[0]}: {got[bad[0]]} != {want[bad[0]]}"
 
 
@@ -97,3 +101,26 @@ def test_lane_body_on_the_families_that_break_readers(driver, tmp_path, name):
     for format, chroma in FORMATS_OF[f.layout][:3]:
         _run(driver, tmp_path, f, planes, format, chroma, 8, "tight", 0)
         _run(driver, tmp_path, f, planes, format, chroma, 300, "pitched", 0)
+
+
+@pytest.mark.parametrize("name", [f.name for f in we.frames()])
+def test_lane_body_on_tables_beyond_the_lds_share(driver, tmp_path, name):
+    """cs.wide_cases / gs.wide_cases at the planner's budget (tests/emul/lut_budget.h): regime B with the direct tables staged
+    in part and the fast mode off, regime C with L2 lookups from global memory beyond entry 12288 -- the driver reports
+    what it staged -- and the control: told that everything is staged, every regime-C frame differs from its expectation."""
+    f = we.frame(name)
+    planes = ps.frame_planes(f)
+    for k, (format, chroma) in enumerate(FORMATS_OF[we.layout_of(f)][:2]):
+        window, destination, shift = VARIANTS[1 + 2 * k] if k < 2 else VARIANTS[0]
+        _run(driver, tmp_path, f, planes, format, chroma, window, destination, shift, luts=we.PLAN)
+        we.check_plan(f)
+        if we.regime(f) == "C" and k == 0:
+            we.check_control(f, _run(driver, tmp_path, f, planes, format, chroma, window, destination, shift, luts=we.BEYOND))
+
+
+def test_ordinary_tables_decode_in_the_fast_mode(driver, tmp_path):
+    f = cs.case("positions/short/422/reference/dri4")
+    format, chroma = FORMATS_OF["422"][0]
+    _run(driver, tmp_path, f, ps.frame_planes(f), format, chroma, 300, "tight", 0)
+    l2 = cs.table_regime(f)["entries"]
+    assert we.REPORTS == [(l2 + 2 * cs.FAST_ENTRIES, l2 + 2 * cs.FAST_ENTRIES, 1)]

@@ -15,6 +15,7 @@ import coef_stream as cs
 import gray_stream as gs
 import planes_stream as ps
 import reduced_stream as rs
+import wide_emul as we
 from conftest import ROOT
 
 SENTINEL, PREFILL, GUARD = 0x5C, 0xA5, 256
@@ -48,7 +49,7 @@ def driver(tmp_path_factory):
     return exe
 
 
-def _run(driver, tmp_path, f, red, format, destination, shift, window):
+def _run(driver, tmp_path, f, red, format, destination, shift, window, luts=()):
     (tmp_path / "in.jpg").write_bytes(f.jpeg())
     comps, hs, vs = ps.sampling_of(f)
     ow = -(-f.w // 8)
@@ -57,7 +58,8 @@ def _run(driver, tmp_path, f, red, format, destination, shift, window):
     flags = (4 if comps == 1 else 1) | (2 if f.standard else 0)
     args = [driver, str(tmp_path / "in.jpg"), str(tmp_path / "out.bin"), str(flags), "3", str(window), str(rs.FORMATS.index(format)),
             str(shift), str(ow), str(oh), str(pt), str(total)]
-    r = subprocess.run(args, capture_output=True, text=True, timeout=120)
+    r = subprocess.run(args + list(luts), capture_output=True, text=True, timeout=120)
+    we.note(r.stderr)
     what = f"{f.name}: {format}, window {window}, {destination}, shift {shift}"
     assert r.returncode == 0 and r.stdout.startswith("ok "), what + "\n" + r.stdout[-500:] + r.stderr[-4000:]
     assert r.stdout.split()[1:] == [str(f.w), str(f.h), str(f.intervals), str(f.interval)], what
@@ -67,6 +69,8 @@ def _run(driver, tmp_path, f, red, format, destination, shift, window):
     got = block[GUARD + shift:-GUARD]
     want = rs.destination(red, f.w, f.h, hs, vs, format, pitch, before=np.full(total, PREFILL, dtype=np.uint8))
     bad = np.flatnonzero(got != want)
+    if "beyond" in luts:
+        return bad.size   # (the control: the caller says what it expects)
     assert not bad.size, f"{what}: {bad.size} bytes differ, first at {bad[0]}: {got[bad[0]]} != {want[bad[0]]}"
 
 
@@ -106,3 +110,24 @@ def test_lane_body_on_the_coefficient_families(driver, tmp_path, name):
     red = rs.frame_reduced(f)
     _run(driver, tmp_path, f, red, "rgba", "pitched", 0, 8)
     _run(driver, tmp_path, f, red, "rgb_planar", "tight", 1, 300)
+
+
+@pytest.mark.parametrize("name", [f.name for f in we.frames()])
+def test_lane_body_on_tables_beyond_the_lds_share(driver, tmp_path, name):
+    """cs.wide_cases / gs.wide_cases at the planner's budget (tests/emul/lut_budget.h): regime B with the direct tables staged
+    in part and the fast mode off, regime C with L2 lookups from global memory beyond entry 12288 -- the driver reports
+    what it staged -- and the control: told that everything is staged, every regime-C frame differs from its expectation."""
+    f = we.frame(name)
+    red = rs.frame_reduced(f)
+    _run(driver, tmp_path, f, red, "rgba", "pitched", 0, 8, luts=we.PLAN)
+    we.check_plan(f)
+    _run(driver, tmp_path, f, red, "rgb_planar", "tight", 1, 300, luts=we.PLAN)
+    if we.regime(f) == "C":
+        we.check_control(f, _run(driver, tmp_path, f, red, "rgb_planar", "tight", 1, 300, luts=we.BEYOND))
+
+
+def test_ordinary_tables_decode_in_the_fast_mode(driver, tmp_path):
+    f = cs.case("random_dense/long/422/reference/dri3")
+    _run(driver, tmp_path, f, rs.frame_reduced(f), "rgba", "tight", 0, 300)
+    l2 = cs.table_regime(f)["entries"]
+    assert we.REPORTS == [(l2 + 2 * cs.FAST_ENTRIES, l2 + 2 * cs.FAST_ENTRIES, 1)]
